@@ -33,9 +33,21 @@ needs a GPU of its own; --share-gpus lets ranks share devices (RCCL then runs
 them as separate "nodes" over its socket transport: a correctness rehearsal
 of the multi-rank path on a one-GPU box, not a performance number).
 
-After the timed steps (outside the timed region) the same engine runs one
-more step with per-phase device timing (kernels / halos / fills / flag
-reductions, --no-phase-step to skip), and then --verify G generations
+A plain run does only what the headline figure needs: it sets up, warms up,
+times the steps, writes its outputs if --dump-outputs DIR is given and prints
+the JSON line (`verified` and the per-phase times are null).
+
+--dump-outputs DIR writes what the last timed step left behind, before
+anything else touches the engine: DIR/cells.npy (float32 0/1, the whole grid
+up to 2^22 cells, else DUMP_ROWS whole rows drawn with a fixed seed),
+DIR/rows.npy (their row numbers) and DIR/step.npy (generation reached,
+generations the last step executed).  The same arguments give the same
+initial grid and the same generation count, so two builds can be compared
+output for output.
+
+With --full, after the timed steps (outside the timed region) the same engine
+runs one more step with per-phase device timing (kernels / halos / fills /
+flag reductions, --no-phase-step to skip), and then --verify G generations
 that are checked bit for bit against an fp32 PyTorch oracle (rolled-copy
 neighbour sums, ops/life_ops.py life_step_torch_roll) and the
 byte-per-cell layout, started from the engine's state at that point:
@@ -146,6 +158,13 @@ ORACLE_BAND_ROWS = 128
 # cells = 16 GiB per byte copy); one rank checks any size on bands read
 # straight from the device (Engine.store_rows), with no whole-grid host copy.
 VERIFY_MAX_CELLS = 1 << 34
+# --dump-outputs: the whole grid up to this many cells (16 MiB of float32),
+# else DUMP_ROWS whole rows drawn without replacement by a generator with a
+# fixed seed; rows wider than DUMP_ROW_CELLS are cut to that many columns.
+DUMP_WHOLE_CELLS = 1 << 22
+DUMP_ROWS = 256
+DUMP_ROW_CELLS = 1 << 15
+DUMP_SEED = 20240229
 
 
 def band_starts(H: int) -> list[int]:
@@ -180,6 +199,43 @@ def band_oracle(snap, r0: int, gens: int, device: str):
     b = min(ORACLE_BAND_ROWS, H)
     rows = np.arange(r0 - gens, r0 + b + gens) % H
     return life_step_torch_roll(snap[rows], gens, device=device)[gens:gens + b]
+
+
+def dump_rows(H: int):
+    """Row numbers --dump-outputs samples from a grid of H rows (ascending)."""
+    import numpy as np  # noqa: PLC0415
+
+    if H <= DUMP_ROWS:
+        return np.arange(H, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(H, DUMP_ROWS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path: str, sim, eng, world: int, rank: int, last) -> None:
+    """--dump-outputs: the cells the last timed step left (what a caller of
+    Engine.run_until reads back), as float32, and that step's report."""
+    import numpy as np  # noqa: PLC0415
+
+    W, H = int(sim.config.width), int(sim.config.height)
+    whole = W * H <= DUMP_WHOLE_CELLS
+    rows = np.arange(H, dtype=np.int64) if whole else dump_rows(H)
+    cols = W if whole else min(W, DUMP_ROW_CELLS)
+    if world > 1:
+        from gol_amd.parallel.dist import gather_grid  # noqa: PLC0415
+
+        grid = gather_grid(sim)  # collective: every rank takes part
+        cells = grid[rows, :cols]
+        del grid
+    elif whole:
+        cells = eng.store_rows(0, H)
+    else:
+        cells = np.concatenate([eng.store_rows(int(r), 1)[:, :cols] for r in rows], axis=0)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "cells.npy"), np.ascontiguousarray(cells, dtype=np.float32))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "step.npy"),
+            np.array([sim.generation, last.executed if last is not None else 0], dtype=np.float64))
 
 
 def dtype_label(layout: str, u8_compute, kernel: str) -> str:
@@ -274,17 +330,26 @@ def parse_args(argv=None):
                          "itself; use with --height H/N to rehearse one rank of an N-GPU run")
     ap.add_argument("--share-gpus", action="store_true",
                     help="let ranks share GPUs (rehearsal of the multi-rank path on fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-phase-timed step and the --verify check "
+                         "(a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the cells the last timed step left (float32, the whole grid or a fixed sample "
+                         "of rows) and that step's generation count as DIR/<name>.npy")
     ap.add_argument("--verify", type=int, default=240,
-                    help="after the timed steps, run G more generations and check them against the fp32 "
-                         "PyTorch oracle and the u8 layout (0: skip)")
+                    help="with --full: after the timed steps, run G more generations and check them against "
+                         "the fp32 PyTorch oracle and the u8 layout (0: skip)")
     ap.add_argument("--verify-bands", action="store_true",
                     help="check on row bands read from the device even below the whole-grid limits "
                          "(one rank: torus bands; several: each rank's own bands, cones from its neighbours)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="runtime tuning (repeatable; python -m gol_amd.cli --tune help lists the keys)")
     ap.add_argument("--no-phase-step", action="store_true",
-                    help="skip the extra per-phase-timed step after the timed ones")
-    return ap.parse_args(argv)
+                    help="with --full: skip the extra per-phase-timed step after the timed ones")
+    a = ap.parse_args(argv)
+    if not a.full:  # a plain run measures the headline figure and nothing else
+        a.verify, a.no_phase_step = 0, True
+    return a
 
 
 def main() -> int:
@@ -378,6 +443,9 @@ def main() -> int:
     S = a.size
     Hg = a.height or S
     gps = max(1, a.gens_per_step)
+    if a.dump_outputs and world > 1 and S * Hg > VERIFY_MAX_CELLS:
+        log(f"bench.py: --dump-outputs on {world} ranks gathers the grid; {S}x{Hg} exceeds {VERIFY_MAX_CELLS} cells")
+        return 2
     extra = (0 if a.no_phase_step else gps) + max(0, a.verify)
     trial_cap = 16384  # prewarm generations allowed beyond --prewarm for the placement trials
     total = a.prewarm + trial_cap + (a.warmup + a.steps * a.repeats) * gps + extra
@@ -409,6 +477,11 @@ def main() -> int:
         while "trial" in eng.overlap_mode() + eng.poll_mode() and trial_gens < trial_cap:
             eng.run_until(sim.generation + 1024)
             trial_gens += 1024
+        # Dumped outputs are compared between builds: the timed steps start at
+        # the same generation however many windows the trials took.
+        if a.dump_outputs and 0 < trial_gens < trial_cap:
+            eng.run_until(sim.generation + trial_cap - trial_gens)
+            trial_gens = trial_cap
     for _ in range(a.warmup):
         step()
     best = None
@@ -427,6 +500,9 @@ def main() -> int:
     gens = max(1, executed)
     value = float(S) * float(Hg) * gens / dt
     stops = sorted({r.stop_reason for r in rs})
+
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sim, eng, world, rank, rs[-1] if rs else None)
 
     # One more step with per-phase device timing (outside the timed region:
     # the event pairs around every operation add a little launch overhead).
@@ -558,6 +634,8 @@ def main() -> int:
             "higher_is_better": True,
             "scaling": "strong",
             "verified": verified,
+            "full": bool(a.full),
+            "dumped_outputs": a.dump_outputs,
             "vs_baseline": value / BASELINE_VALUE,
             "dtype": dtype_label(a.layout, desc["u8_compute"], desc["kernel"]),
             "data": "synthetic: on-device counter-based RNG random grid, density 0.5 (generate.sh distribution)",

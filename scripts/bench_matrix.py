@@ -56,7 +56,9 @@ def main() -> int:
     log = open(os.path.splitext(a.out)[0] + ".log", "a")
     for run in range(a.repeat):
         for name, env, args in rows:
-            cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), *args]
+            # --full: the records keep the per-phase step and the verification
+            # (verified, final_sha256) unless the line's own arguments turn them off.
+            cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--full", *args]
             print(f"[{time.strftime('%H:%M:%S')}] run {run} {name}: {' '.join(args)} {env}", flush=True)
             e = dict(os.environ)
             e.update(env)

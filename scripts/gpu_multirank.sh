@@ -9,6 +9,6 @@ timeout -k 10 900 python -u -m pytest tests/test_rccl_multirank.py tests/test_gp
   --timeout-method thread -k "rccl or multirank or links_only or rehearsal or share" > $O/pytest.log 2>&1 \
   || { tail -60 $O/pytest.log; exit 1; }
 tail -3 $O/pytest.log
-timeout -k 10 600 python -u bench.py --gpus 8 --share-gpus --steps 3 --warmup 1 --prewarm 2000 --verify 96 \
+timeout -k 10 600 python -u bench.py --gpus 8 --share-gpus --steps 3 --warmup 1 --prewarm 2000 --full --verify 96 \
   > $O/bench_8ranks_shared.json 2> $O/bench_8ranks_shared.err || { tail -40 $O/bench_8ranks_shared.err; exit 1; }
 cat $O/bench_8ranks_shared.json

@@ -12,7 +12,7 @@ mkdir -p "$O"
 run() {  # name, bench.py arguments...
   local n=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$n" -o run -- \
-    python3 bench.py "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -30 "$O/$n.err"; return 1; }
+    python3 bench.py --full "$@" >"$O/$n.json" 2> "$O/$n.err" || { tail -30 "$O/$n.err"; return 1; }
   python3 scripts/summarize_profile.py "$O/$n" > "$O/$n.md" || return 1
   echo "$n ok: $(python3 -c "import json,sys; r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(r['ms_per_step'], r['value'], r.get('verified'))" "$O/$n.json")"
 }

@@ -38,7 +38,7 @@ def _bench(args, env_extra=None, timeout=300):
 
 
 SMALL = ["--engine", "cpu", "--size", 256, "--steps", 3, "--warmup", 1, "--gens-per-step", 100, "--prewarm", 16,
-         "--verify", 40]
+         "--full", "--verify", 40]
 
 
 @pytest.mark.parametrize("gpus", [1, 4, 8])
@@ -66,6 +66,42 @@ def test_bench_gpus_n_launches_n_ranks_itself(native, gpus):
     # 256^2 is BASELINE config 1's grid, not the headline metric.
     assert rec["headline"] is False and rec["config_id"] == 1
     assert rec["metric"] == "cell-updates/sec (whole node), 256^2 x 100 gens"
+
+
+@pytest.mark.parametrize("gpus,size,height", [(1, 256, 192), (2, 4096, 1100)])
+def test_bench_plain_run_times_only_and_dumps_its_outputs(native, tmp_path, gpus, size, height):
+    """Without --full the run stops after the timed steps (no per-phase step,
+    no verification); --dump-outputs writes the cells the last timed step
+    left - the whole grid when small, else a fixed sample of whole rows - and
+    they are the cells of the same seed advanced that many generations."""
+    args = ["--gpus", gpus, "--engine", "cpu", "--size", size, "--height", height, "--steps", 2, "--warmup", 1,
+            "--gens-per-step", 20, "--prewarm", 8, "--seed", 5, "--dump-outputs", tmp_path / "out"]
+    r = _bench(args)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads(r.stdout)
+    assert rec["full"] is False and rec["verified"] is None
+    assert rec["config"]["verify"] is None and rec["config"]["phase_ms_one_step"] is None
+    assert rec["steps"] == 2 and rec["config"]["generations_timed"] == 40 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - size * height * 40 / (rec["ms_per_step"] * 2e-3)) < 1e-6 * rec["value"]
+    out = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert sorted(out) == ["cells", "rows", "step"]
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    gen, last = map(int, out["step"])
+    assert last == 20 and gen >= 8 + 3 * 20
+    rows = out["rows"].astype(np.int64)
+    whole = size * height <= 1 << 22
+    assert len(rows) == (height if whole else 256) and (np.diff(rows) > 0).all() and rows[-1] < height
+    sim = Simulation(LifeConfig(size, height, gen_limit=gen, check_similarity=False), engine="cpu")
+    sim.init_random(5, 0.5)
+    sim.advance(gen)
+    assert out["cells"].shape == (len(rows), size)
+    assert np.array_equal(out["cells"], sim.tile()[rows].astype(np.float32))
+    # the same arguments dump the same arrays
+    r2 = _bench([*args[:-1], tmp_path / "again"])
+    assert r2.returncode == 0, r2.stderr[-3000:]
+    for k, a in out.items():
+        assert np.array_equal(a, np.load(tmp_path / "again" / f"{k}.npy")), k
 
 
 @pytest.mark.parametrize("height,drift", [(256, "0"), (192, "1")])
@@ -350,7 +386,7 @@ def test_bench_dtype_label_says_what_the_loop_computes_on(native, layout, u8c, w
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--engine", "cpu", "--size", "128", "--steps", "1",
-                        "--warmup", "0", "--gens-per-step", "32", "--prewarm", "0", "--verify", "16",
+                        "--warmup", "0", "--gens-per-step", "32", "--prewarm", "0", "--full", "--verify", "16",
                         "--layout", layout, "--u8-compute", u8c], capture_output=True, text=True, timeout=300,
                        env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -61,7 +61,7 @@ def test_torchrun_terminating_run(native, tmp_path):
 def test_bench_cpu_dry_run_two_ranks(native, tmp_path):
     r = _torchrun(2, [str(REPO / "bench.py"), "--gpus", "2", "--engine", "cpu", "--comm", "torch",
                       "--size", "256", "--steps", "3", "--warmup", "1", "--gens-per-step", "100",
-                      "--prewarm", "16"], tmp_path)
+                      "--prewarm", "16", "--full"], tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -107,7 +107,7 @@ def test_bench_multirank_band_verifier(native, tmp_path, nproc, layout, overlap)
     takes, where no host can gather the grid."""
     args = [str(REPO / "bench.py"), "--gpus", str(nproc), "--engine", "cpu", "--comm", "torch",
             "--size", "256", "--height", str(96 * nproc), "--layout", layout, "--steps", "1", "--warmup", "0",
-            "--gens-per-step", "64", "--prewarm", "0", "--verify", "40", "--verify-bands", "--overlap", overlap,
+            "--gens-per-step", "64", "--prewarm", "0", "--full", "--verify", "40", "--verify-bands", "--overlap", overlap,
             "--tune", "cpu_trigger=1"]
     r = _torchrun(nproc, args, tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,9 +1,11 @@
 """T2 golden semantics against the reference itself: the
-reference's serial src/game.c is compiled in a scratch directory (never
-vendored) and run on the same input file as `bin/gol`; the output file must
-be byte-identical and the "Generations:" line equal.  The serial reference
-indexes [y][x] and is only correct for square grids (README.md:61), so the
-grids are square."""
+reference's serial src/game.c and `bin/gol` run on the same input file; the
+output file must be byte-identical and the "Generations:" line equal.  The
+reference's side is its recorded runs (tests/golden/game_c, written by
+tests/make_game_c_fixtures.py), or, where GOL_REFERENCE_GAME_C names the
+source file, a build of it in a scratch directory (never vendored).  The
+serial reference indexes [y][x] and is only correct for square grids
+(README.md:61), so the grids are square."""
 import gzip
 import json
 import subprocess
@@ -18,6 +20,7 @@ from conftest import generations_line, run_reference_serial
 from golden import CASES
 
 GRIDS = [(96, 1, 0.5), (256, 2, 0.5), (64, 11, 0.2), (40, 14, 0.2), (48, 7, 0.3), (33, 4, 0.35)]
+STDOUT_GRID = (32, 3, 0.5)  # test_stdout_contract_serial's input
 
 
 def _run_ours(gol_bin, workdir, N, path, *extra):
@@ -56,11 +59,12 @@ def test_golden_patterns_match_reference_game_c(reference_serial, gol_bin, tmp_p
 def test_stdout_contract_serial(reference_serial, gol_bin, tmp_path):
     """Same stdout lines as game.c (only the timing value differs)."""
     f = tmp_path / "in.txt"
-    io.generate(str(f), 32, 32, seed=3)
+    N, seed, density = STDOUT_GRID
+    io.generate(str(f), N, N, seed=seed, density=density)
     (tmp_path / "a").mkdir()
     (tmp_path / "b").mkdir()
-    ref_out, _ = run_reference_serial(reference_serial, tmp_path / "a", 32, 32, f)
-    our_out, _ = _run_ours(gol_bin, tmp_path / "b", 32, f, "--engine", "cpu")
+    ref_out, _ = run_reference_serial(reference_serial, tmp_path / "a", N, N, f)
+    our_out, _ = _run_ours(gol_bin, tmp_path / "b", N, f, "--engine", "cpu")
     strip = lambda s: [ln.split("\t")[0] for ln in s.splitlines()]  # noqa: E731
     assert strip(our_out) == strip(ref_out)
 
@@ -74,8 +78,8 @@ def test_output_bytes_match_reference_game_c_on_gpu(reference_serial, gol_bin, t
 
 
 # Recorded outputs of the same reference build on the same GRIDS inputs
-# (tests/make_game_c_fixtures.py), for boxes without the reference mount.
-FIXTURES = Path(__file__).resolve().parent / "fixtures" / "game_c"
+# (tests/make_game_c_fixtures.py), by name.
+FIXTURES = Path(__file__).resolve().parent / "golden" / "game_c"
 
 
 def _fixture(N, seed, density):

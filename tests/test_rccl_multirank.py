@@ -61,7 +61,7 @@ def test_bench_launches_its_own_ranks_on_gpu(gpu):
     (RCCL halos, shared GPU rehearsal), relays one JSON line with n_gpus 2,
     and the verification gate passes."""
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--share-gpus", "--size", "2048",
-           "--steps", "2", "--warmup", "1", "--gens-per-step", "200", "--prewarm", "4000", "--verify", "100"]
+           "--steps", "2", "--warmup", "1", "--gens-per-step", "200", "--prewarm", "4000", "--full", "--verify", "100"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -86,7 +86,7 @@ def test_bench_node_rehearsal_8_ranks_full_grid(gpu):
     own RCCL process group (timing MAX, all_gather of the 32768^2 grid), the
     overlap auto trial and the fp32 oracle verify."""
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "8", "--share-gpus", "--steps", "2", "--warmup", "1",
-           "--prewarm", "0", "--verify", "48"]
+           "--prewarm", "0", "--full", "--verify", "48"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -168,7 +168,7 @@ def test_bench_records_tuning(native):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--engine", "cpu", "--size", "256", "--steps", "2",
-                        "--warmup", "1", "--gens-per-step", "64", "--prewarm", "0", "--verify", "32",
+                        "--warmup", "1", "--gens-per-step", "64", "--prewarm", "0", "--full", "--verify", "32",
                         "--tune", "cpu_ring=1", "--tune", "host_threads=2"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
