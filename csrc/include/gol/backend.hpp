@@ -10,6 +10,7 @@
 
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "gol/tile.hpp"
 #include "gol/tuning.hpp"
@@ -151,8 +152,17 @@ class Backend {
     bool drift = false;
     bool link = false;  // consecutive blocks may run linked (BlockArgs::link)
   };
-  virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req) const {
+  virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req,
+                                     Rule /*rule*/ = Rule{}) const {
     return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l)};
+  }
+  // Whether run_block evaluates `rule` (BlockArgs::rule) on tiles of this
+  // layout.  The CPU backend runs any rule without B0; the HIP backend the
+  // rules compiled from csrc/kernels/life_rules.def.  unsupported_rule() is
+  // the message of the engine's refusal.
+  virtual bool supports_rule(Layout, Rule rule) const { return rule_is_default(rule); }
+  virtual std::string unsupported_rule(Layout, Rule rule) const {
+    return "backend " + name() + " does not run rule " + rule_string(rule);
   }
   // Row ring (single-rank torus): a tile whose top Dv halo rows are a second
   // virtual mapping of its last Dv owned rows and whose bottom halo rows map
@@ -207,6 +217,9 @@ std::unique_ptr<Backend> make_cpu_backend(int threads, int drift = -1, const Tun
 // or if `tune` selects a kernel that does not exist.
 std::unique_ptr<Backend> make_hip_backend(int device, const Tuning& tune = Tuning::from_env());
 bool hip_available();
+// The Life-like rules compiled for the HIP engine besides B3/S23
+// (csrc/kernels/life_rules.def).
+std::vector<Rule> hip_rules();
 
 // Counter-based RNG used by init_random (host and device agree bit-for-bit).
 GOL_HD inline uint64_t splitmix64(uint64_t x) {

@@ -35,6 +35,10 @@ struct CheckpointMeta {
   bool check_similarity = true;
   int sim_freq = 3;
   std::string layout = "auto";
+  // Life-like rule, canonical text.  meta.json carries a "rule" key only when
+  // it is not B3/S23 (checkpoints of the default rule are unchanged byte for
+  // byte); a missing key means B3/S23.
+  std::string rule = "B3/S23";
   std::string grid = "grid.txt";  // grid file name inside the checkpoint directory
 };
 

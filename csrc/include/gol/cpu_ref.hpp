@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "gol/common.hpp"
+
 namespace gol {
 
 struct RefResult {
@@ -18,8 +20,10 @@ struct RefResult {
 
 // `grid` holds H*W cells (0/1 or ASCII) and is overwritten with the final
 // generation as 0/1 bytes.  threads > 1 splits the rows like the
-// reference's OpenMP build (src/game_openmp.c:34).
+// reference's OpenMP build (src/game_openmp.c:34).  `rule`: any Life-like
+// rule without B0, applied by its plain per-cell definition (the reference
+// itself is B3/S23 only): the exact oracle for "Generations" under any rule.
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
-                            bool check_similarity, int sim_freq, int threads);
+                            bool check_similarity, int sim_freq, int threads, Rule rule = Rule{});
 
 }  // namespace gol

@@ -5,7 +5,8 @@
 // CUDA src/game_cuda.cu:213-276.  All of them test termination every
 // generation (a full scan + MPI_Allreduce, or a kernel + 4-byte D2H copy).
 // Both stop conditions are absorbing: an empty grid stays
-// empty and G_t == G_{t-1} implies G_{t+k} == G_t.  So the kernels record
+// empty (for every rule without B0, which is why B0 rules are refused) and
+// G_t == G_{t-1} implies G_{t+k} == G_t (for any rule).  So the kernels record
 // one "changed" flag per generation, the engine polls them every few hundred
 // generations, and the reference's reported generation count is rebuilt
 // exactly from the first unchanged generation g_f:
@@ -29,6 +30,7 @@ namespace gol {
 struct EngineConfig {
   int64_t W = 0, H = 0;            // global grid (cells)
   Layout layout = Layout::Bits;
+  Rule rule;                       // Life-like rule (common.hpp), default B3/S23; no B0
   std::string decomp = "auto";     // "auto" or "PxQ"
   int64_t gen_limit = 1000;        // GEN_LIMIT (src/game.c:6)
   bool check_similarity = true;    // CHECK_SIMILARITY (src/game.c:8)

@@ -64,6 +64,7 @@ struct BlockArgs {
   TileGeom g;
   int64_t row_lo = 0, row_hi = 0;
   int T = 1;
+  Rule rule;  // the engine's (EngineConfig::rule); default B3/S23
   int64_t gen_base = 0;
   uint32_t* changed = nullptr;
   int64_t flags_base = 0;

@@ -17,6 +17,46 @@ const char* xlane_name(int x) { return x == kXlaneAuto ? "auto(add|dpp)" : x == 
 
 }  // namespace
 
+// The rule kernels (life_rule_<name>_<variant>.hip), one table generated from
+// life_rules.def.
+#define GOL_RULE(name, B, S)                          \
+  GOL_LIFE_VARIANT(launch_rule_##name##_bits_dpp);    \
+  GOL_LIFE_VARIANT(launch_rule_##name##_bits_add);    \
+  GOL_LIFE_VARIANT(launch_rule_##name##_u8_dpp);
+#include "life_rules.def"
+#undef GOL_RULE
+
+namespace {
+
+using VariantFn = void (*)(const LifeBlockParams&, int64_t, int, const LifeTuning&, hipStream_t);
+struct RuleKernels {
+  const char* name;
+  Rule rule;
+  VariantFn bits_dpp, bits_add, u8_dpp;
+};
+const RuleKernels kRuleKernels[] = {
+#define GOL_RULE(name, B, S) \
+  {#name, Rule{B, S}, launch_rule_##name##_bits_dpp, launch_rule_##name##_bits_add, launch_rule_##name##_u8_dpp},
+#include "life_rules.def"
+#undef GOL_RULE
+};
+
+const RuleKernels* rule_kernels(Rule r) {
+  for (const RuleKernels& k : kRuleKernels)
+    if (k.rule == r) return &k;
+  return nullptr;
+}
+
+}  // namespace
+
+std::vector<Rule> life_block_rules() {
+  std::vector<Rule> v;
+  for (const RuleKernels& k : kRuleKernels) v.push_back(k.rule);
+  return v;
+}
+
+bool life_block_has_rule(Rule r) { return rule_is_default(r) || rule_kernels(r) != nullptr; }
+
 std::string life_block_variant(Layout layout, const LifeTuning& tune) {
   if (layout == Layout::U8 && tune.u8_lds)
     return tune.lds_T > 1 ? "u8 lds-tiled T=" + std::to_string(tune.lds_T) + (tune.lds_pack && tune.lds_T >= 8 ? " packed" : "")
@@ -71,6 +111,20 @@ int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t st
   p.fault_delay = tune.fault_delay;
   const int64_t rows = a.row_hi - a.row_lo;
   int x = tune.xlane == kXlaneAdd || tune.xlane == kXlaneAuto ? tune.xlane : kXlaneDpp;
+  // Any rule but B3/S23: the kernels compiled from life_rules.def.
+  const RuleKernels* rk = nullptr;
+  if (!rule_is_default(a.rule)) {
+    rk = rule_kernels(a.rule);
+    if (!rk) {
+      std::string have;
+      for (const RuleKernels& k : kRuleKernels) have += std::string(have.empty() ? "" : ", ") + rule_string(k.rule);
+      fail("rule " + rule_string(a.rule) + " is not compiled for the HIP engine (compiled: B3/S23, " + have +
+           "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)");
+    }
+    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds),
+                "life_block: the LDS-tiled byte kernels run B3/S23 only (u8_kernel=lds with a rule)");
+    GOL_REQUIRE(a.T <= 16, "life_block: rule kernels run temporal blocks of at most 16 generations");
+  }
   if (g.layout == Layout::U8 && tune.u8_lds && (a.T == 1 || a.T == 2 || a.T == 4 || a.T == 8 || a.T == 16 || a.T == 32)) {
     // Packed tiles need 32-cell aligned rows (pitch) and owned cells.
     const bool pack = a.T >= 8 && (tune.lds_pack || a.T > 8) && g.pitch % 32 == 0 && g.cell0() % 32 == 0;
@@ -91,6 +145,15 @@ int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t st
   // word per pass, so passes deeper than 16 (the byte layout's T = 24 / 32)
   // run the DPP window.
   if (x == kXlaneAdd && !(a.allow_drift && a.T <= 16 && (p.wrap_w > 0 || 32 * g.hw >= 2 * a.T))) x = kXlaneDpp;
+  if (rk) {
+    // No byte-layout adder variant: that request runs the DPP window.
+    if (x == kXlaneAdd && g.layout == Layout::Bits) {
+      rk->bits_add(p, rows, a.T, tune, stream);
+      return a.T;
+    }
+    (g.layout == Layout::U8 ? rk->u8_dpp : rk->bits_dpp)(p, rows, a.T, tune, stream);
+    return 0;
+  }
   if (x == kXlaneAdd) {
     (g.layout == Layout::U8 ? launch_u8_w1_add : launch_bits_w1_add)(p, rows, a.T, tune, stream);
     return a.T;

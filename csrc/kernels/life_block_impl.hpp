@@ -265,12 +265,60 @@ __device__ __forceinline__ uint32_t rule(uint32_t a0, uint32_t a1, uint32_t b0, 
   return bop3<tt::SEL>(x0, s3, ctr & s4);
 }
 
+// ---- rule policies (the IO policies' Rule parameter) -------------------------
+// Conway: the B3/S23 fast form above (7 bitop3 and one AND).
+struct Conway {
+  static constexpr bool kDefault = true;
+  __device__ static __forceinline__ uint32_t eval(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                                  uint32_t c1, uint32_t ctr) {
+    return rule(a0, a1, b0, b1, c0, c1, ctr);
+  }
+};
+
+// Any other Life-like rule (birth / survive masks, gol::Rule): the general
+// form of common.hpp rule_host(Rule, ...), its truth tables and s3 patches
+// folded at compile time.  9 ops; 8 without survivals; +2 or +3 where S = 8, 9
+// need a patch (rule_tables).
+template <unsigned B, unsigned S>
+struct LifeLike {
+  static constexpr bool kDefault = false;
+  static constexpr gol::Rule kRule{uint16_t(B), uint16_t(S)};
+  static constexpr RuleTables kT = rule_tables(kRule);
+  static_assert((B & 1u) == 0, "B0 rules are not supported");
+  static_assert(!(kRule == gol::Rule{}), "B3/S23 runs the Conway form");
+  __device__ static __forceinline__ uint32_t eval(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                                  uint32_t c1, uint32_t ctr) {
+    const uint32_t x0 = bop3<tt::XOR3>(a0, b0, c0);
+    const uint32_t x1 = bop3<tt::MAJ>(a0, b0, c0);
+    const uint32_t y0 = bop3<tt::XOR3>(a1, b1, c1);
+    const uint32_t y1 = bop3<tt::MAJ>(a1, b1, c1);
+    const uint32_t s1 = x1 ^ y0;
+    const uint32_t s2 = bop3<tt::XOR_AND>(x1, y0, y1);
+    uint32_t s3 = 0u;
+    if constexpr (kT.needs_s3()) s3 = bop3<tt::AND3>(x1, y0, y1);
+    uint32_t fb = bop3<kT.fb>(s2, s1, x0);
+    if constexpr (kT.b8) fb |= s3;
+    uint32_t nxt;
+    if constexpr (S == 0) {
+      nxt = fb & ~ctr;
+    } else {
+      uint32_t fs = bop3<kT.fs>(s2, s1, x0);
+      if constexpr (kT.s9_set) fs = bop3<tt::OR_AND>(fs, s3, x0);
+      if constexpr (kT.s9_clr) fs = bop3<tt::ANDN_AND>(fs, s3, x0);
+      nxt = bop3<tt::SEL>(ctr, fs, fb);
+    }
+    if constexpr (kT.post_or) nxt |= s3;
+    return nxt;
+  }
+};
+
 // ---- storage layouts -------------------------------------------------------
 // load_raw() issues the global loads for one lane's W words of a row;
 // convert() turns them into bit words.  Splitting the two lets the row reader
 // keep three rows of loads in flight.
-template <int W_, int XL_>
+template <int W_, int XL_, class Rule_ = Conway>
 struct BitsIO {
+  using Rule = Rule_;
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = 1;  // halo lanes per wave side
   static constexpr bool kLinked = false;  // Sc1IO
@@ -310,8 +358,9 @@ struct BitsIO {
 #define GOL_U8_LOAD_NT 0
 #endif
 
-template <int W_, int XL_, int HALO_ = 1>
+template <int W_, int XL_, int HALO_ = 1, class Rule_ = Conway>
 struct U8IO {
+  using Rule = Rule_;
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = HALO_;  // halo lanes per wave side (2: passes deeper than 32)
   static constexpr bool kLinked = false;  // Sc1IO
@@ -458,8 +507,8 @@ __device__ __forceinline__ Vec<W> level_full(Levels<T, W>& st, const Vec<W>& cur
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     const uint32_t ctr = st.cc[L][s2].w[i];
-    nxt.w[i] = rule(st.h0[L][s1].w[i], st.h1[L][s1].w[i], st.h0[L][s2].w[i], st.h1[L][s2].w[i], h0.w[i],
-                    h1.w[i], ctr);
+    nxt.w[i] = IO::Rule::eval(st.h0[L][s1].w[i], st.h1[L][s1].w[i], st.h0[L][s2].w[i], st.h1[L][s2].w[i], h0.w[i],
+                              h1.w[i], ctr);
     st.acc[L].w[i] = bop3<tt::OR_XOR>(st.acc[L].w[i], nxt.w[i], ctr);
     // Opaque def: in straight-line code (prologue / grouped epilogue) hipcc
     // otherwise reassociates the flag ORs of many steps into one late tree

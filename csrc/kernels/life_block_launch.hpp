@@ -150,7 +150,7 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
   // tiles, whose launches alone hold 2 waves per SIMD).  Any other launch
   // first joins the two streams.
   if (tune.link) {
-    if constexpr (IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
+    if constexpr (IO::Rule::kDefault && IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
                   (IO::XL == kXlaneDpp || IO::XL == kXlaneAdd)) {
       if (tune.group != 0) {
         // Blocks of T <= 8 link 4-wave groups where the unlinked path would
@@ -197,7 +197,8 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
       // global memory, so no wave carries a redundant triangle but the
       // strip's last.  Stream launches only (the flags count launches, so a
       // replayed graph would see its own stale flags).
-      if (tune.chain && tune.chain_ok && tune.chain_mem && tune.chain_seq) {
+      // Rule kernels (IO::Rule other than Conway) are never linked or chained.
+      if (IO::Rule::kDefault && tune.chain && tune.chain_ok && tune.chain_mem && tune.chain_seq) {
         LifeBlockParams ch = p;
         ch.fold = 1;
         ch.fold_lanes = 64;
@@ -260,13 +261,13 @@ void launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, const Lif
     case 16: launch_T<16, IO>(p, out_rows, tune, s); break;
     case 24:  // byte layout only: fewer byte-grid passes per generation
       // (the adder window never runs T > 16: launch_life_block switches it to DPP)
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd) {
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault) {
         launch_deep<24, IO>(p, out_rows, tune, s);
         break;
       }
       [[fallthrough]];
     case 32:
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd) {
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault) {
         if (T == 32) {
           launch_deep<32, IO>(p, out_rows, tune, s);
           break;
@@ -280,3 +281,33 @@ void launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, const Lif
 }  // namespace lb
 }  // namespace hipk
 }  // namespace gol
+
+// Life-like rule kernels: one translation unit per rule of life_rules.def and
+// variant (bit layout with the DPP or the adder window, byte layout with the
+// DPP window), life_rule_<name>_<variant>.hip, each one line:
+//   GOL_RULE_TU_BITS_DPP(name) | GOL_RULE_TU_BITS_ADD(name) | GOL_RULE_TU_U8_DPP(name)
+namespace gol {
+namespace hipk {
+namespace lb {
+namespace rules {
+#define GOL_RULE(name, B, S) constexpr unsigned kB_##name = B, kS_##name = S;
+#include "life_rules.def"
+#undef GOL_RULE
+}  // namespace rules
+}  // namespace lb
+}  // namespace hipk
+}  // namespace gol
+#define GOL_RULE_TU(name, variant, IO_, XL_)                                                   \
+  namespace gol {                                                                              \
+  namespace hipk {                                                                             \
+  GOL_LIFE_VARIANT(launch_rule_##name##_##variant) {                                           \
+    using R = lb::LifeLike<lb::rules::kB_##name, lb::rules::kS_##name>;                        \
+    lb::launch_variant<IO_(XL_, R)>(p, out_rows, T, tune, s);                                  \
+  }                                                                                            \
+  }                                                                                            \
+  }
+#define GOL_RULE_IO_BITS(XL_, R_) lb::BitsIO<1, XL_, R_>
+#define GOL_RULE_IO_U8(XL_, R_) lb::U8IO<1, XL_, 1, R_>
+#define GOL_RULE_TU_BITS_DPP(name) GOL_RULE_TU(name, bits_dpp, GOL_RULE_IO_BITS, kXlaneDpp)
+#define GOL_RULE_TU_BITS_ADD(name) GOL_RULE_TU(name, bits_add, GOL_RULE_IO_BITS, kXlaneAdd)
+#define GOL_RULE_TU_U8_DPP(name) GOL_RULE_TU(name, u8_dpp, GOL_RULE_IO_U8, kXlaneDpp)

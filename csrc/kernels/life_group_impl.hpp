@@ -308,6 +308,9 @@ __device__ __forceinline__ void epilogue_tri(Levels<T, IO::W>& st, RowReader<IO>
 template <int T, class IO>
 constexpr int group_min_waves() {
   if constexpr (IO::W >= 2) return T >= 12 ? 2 : T >= 8 ? 3 : 4;
+  // Rule kernels (two more ops per level body) would spill at T = 16 under
+  // the 128-VGPR cap: they keep 3 waves/SIMD there.  Their default is T = 12.
+  if constexpr (IO::XL == kXlaneAdd && T >= 16 && !IO::Rule::kDefault) return 3;
   if constexpr (IO::XL == kXlaneAdd) return T >= 16 ? GOL_GROUP_T16_ADD_WAVES : T >= 12 ? GOL_GROUP_T12_ADD_WAVES : 4;
   return T >= 16 ? GOL_GROUP_T16_WAVES : T >= 12 ? 3 : 4;
 }
@@ -342,7 +345,8 @@ void life_group_kernel(const LifeBlockParams p) {
   // recomputes its upper neighbour's last row, identically), so the wave's
   // control flow is the same for all of them; lanes carry their group's row
   // offset in their read / store offsets.
-  const bool chain = p.chain_buf != nullptr;  // fold == 1 (launch_T)
+  // fold == 1 (launch_T); rule kernels are never chained (the wait compiles out)
+  const bool chain = IO::Rule::kDefault && p.chain_buf != nullptr;
   int kcol, grp, nsub = 1, sub_lanes = 64;
   if (p.fold > 1 && blk >= (p.ncolw - 1) * p.nseg) {
     kcol = p.ncolw - 1;

@@ -5,6 +5,7 @@
 
 #include <functional>
 #include <string>
+#include <vector>
 
 #include "gol/tile.hpp"
 
@@ -208,6 +209,10 @@ struct LifeTuning {
 // Returns the storage-frame drift of the launch in cells (T for the adder
 // window, 0 otherwise; BlockArgs::allow_drift).
 int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t stream);
+// The Life-like rules compiled for the HIP engine besides B3/S23
+// (life_rules.def), and whether launch_life_block runs `r`.
+std::vector<Rule> life_block_rules();
+bool life_block_has_rule(Rule r);
 // Description of the kernel variant the tuning selects for a layout.
 std::string life_block_variant(Layout layout, const LifeTuning& tune);
 // Largest T that keeps 2 waves/SIMD for the variant's words-per-lane.

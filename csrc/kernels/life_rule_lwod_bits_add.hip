@@ -1,0 +1,4 @@
+// Rule kernels of lwod (life_rules.def), variant bits_add: see life_block_launch.hpp.
+#include "life_block_launch.hpp"
+
+GOL_RULE_TU_BITS_ADD(lwod)

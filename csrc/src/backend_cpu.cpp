@@ -79,6 +79,36 @@ GOL_ROW_CLONES uint32_t rule_row(const uint32_t* a0, const uint32_t* a1, const u
   return acc;
 }
 
+// The same for any Life-like rule (gol::Rule masks, taken at run time): the
+// four bits of S as plain word expressions, then one equality mask per
+// neighbour count the rule names.  A dead centre is born at S == n for n in
+// birth, a live one survives at S == n + 1 for n in survive.  Written from
+// the rule's definition, not from the kernels' truth tables (rule_tables), so
+// it stays an independent oracle for them.
+GOL_ROW_CLONES uint32_t rule_row(Rule rule, const uint32_t* a0, const uint32_t* a1, const uint32_t* b0,
+                                 const uint32_t* b1, const uint32_t* c0, const uint32_t* c1, const uint32_t* mid,
+                                 int64_t Wp, const uint32_t* owned, uint32_t* out) {
+  uint32_t acc = 0;
+  for (int64_t c = 0; c < Wp; ++c) {
+    const uint32_t p0 = a0[c] ^ b0[c], p1 = a1[c] ^ b1[c];
+    const uint32_t x0 = p0 ^ c0[c], x1 = (a0[c] & b0[c]) | (c0[c] & p0);
+    const uint32_t y0 = p1 ^ c1[c], y1 = (a1[c] & b1[c]) | (c1[c] & p1);
+    const uint32_t cy = x1 & y0;
+    const uint32_t s[4] = {x0, x1 ^ y0, cy ^ y1, cy & y1};
+    uint32_t born = 0, stay = 0;
+    for (int k = 0; k <= 9; ++k) {
+      uint32_t is_k = ~0u;  // cells with S == k
+      for (int j = 0; j < 4; ++j) is_k &= ((k >> j) & 1) ? s[j] : ~s[j];
+      if (k <= 8 && ((rule.birth >> k) & 1u)) born |= is_k;
+      if (k >= 1 && ((rule.survive >> (k - 1)) & 1u)) stay |= is_k;
+    }
+    const uint32_t nw = (~mid[c] & born) | (mid[c] & stay);
+    out[c] = nw;
+    acc |= (nw ^ mid[c]) & owned[c];
+  }
+  return acc;
+}
+
 // Mask of owned cells inside padded word c.
 inline uint32_t owned_mask(const TileGeom& g, int64_t c) {
   int64_t lo = g.cell0(), hi = g.cell0() + g.W;
@@ -158,6 +188,8 @@ class CpuBackend final : public Backend {
     return drift_ ? "cpu [drift]" : "cpu";
   }
   bool drifts(Layout) const override { return drift_; }
+  // Any Life-like rule (B0 is refused by the engine itself).
+  bool supports_rule(Layout, Rule) const override { return true; }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override;
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t r0,
                     int64_t n) override;
@@ -262,6 +294,7 @@ int CpuBackend::run_block(const BlockArgs& a) {
   // Level rows outside the band are recomputed by both neighbours; every
   // computed row is a valid row, so the per-band change flags OR together
   // into the block's per-generation flags exactly.
+  const bool conway = rule_is_default(a.rule);
   const int64_t out_rows = a.row_hi - a.row_lo;
   const int64_t bs = std::max<int64_t>(4 * int64_t(T), ceil_div(out_rows, 2 * int64_t(pool_.size())));
   const int64_t nb = ceil_div(out_rows, bs);
@@ -307,8 +340,10 @@ int CpuBackend::run_block(const BlockArgs& a) {
           const bool last = L + 1 == T;
           const int64_t sd = last ? 0 : cnt[size_t(L + 1)] % 3;
           uint32_t* dst = last ? &outrow[1] : cells(L + 1, sd);
-          acc[size_t(L)] |= rule_row(hs0(L, sa), hs1(L, sa), hs0(L, sb), hs1(L, sb), hs0(L, sc), hs1(L, sc),
-                                     cells(L, sb), Wp, owned.data(), dst);
+          acc[size_t(L)] |= conway ? rule_row(hs0(L, sa), hs1(L, sa), hs0(L, sb), hs1(L, sb), hs0(L, sc), hs1(L, sc),
+                                              cells(L, sb), Wp, owned.data(), dst)
+                                   : rule_row(a.rule, hs0(L, sa), hs1(L, sa), hs0(L, sb), hs1(L, sb), hs0(L, sc),
+                                              hs1(L, sc), cells(L, sb), Wp, owned.data(), dst);
           if (!last) {
             hsum_row(dst, Wp, hs0(L + 1, sd), hs1(L + 1, sd));
             ++cnt[size_t(L + 1)];

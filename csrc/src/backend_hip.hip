@@ -598,8 +598,11 @@ class HipBackend final : public Backend {
     const bool capturing = capturing_;  // capture_begin / capture_end (no query per launch)
     // A launch may join a linked chain only outside a capture, for the bit
     // layout; anything else first joins.
-    const bool linkable =
-        (link_on_ || (a.link && link_mode_ < 0)) && link_.stream[1] && !capturing && a.g.layout == Layout::Bits;
+    // Rule kernels (any rule but B3/S23) are never linked or chained, forced
+    // link=1 / chain=1 included.
+    const bool conway = rule_is_default(a.rule);
+    const bool linkable = conway && (link_on_ || (a.link && link_mode_ < 0)) && link_.stream[1] && !capturing &&
+                          a.g.layout == Layout::Bits;
     if (!linkable) join_streams();
     tune_.link = linkable ? &link_ : nullptr;
     if (chain_mode_) {  // chained groups: own stream only, never inside a graph capture
@@ -625,12 +628,15 @@ class HipBackend final : public Backend {
       link_.bnd_count = trigger_counter();
     }
     Pending* timed = nullptr;
-    if (chain_mode_ < 0 && !linkable) timed = autotune_chain(a);
+    if (chain_mode_ < 0 && !linkable && conway) timed = autotune_chain(a);
     if (linkable) tune_.chain = 0;
+    const int chain_kept = tune_.chain;
+    if (!conway) tune_.chain = 0;
     if (timed) HIP_CHECK(hipEventRecord(timed->e0, s));
     const auto l0 = prof_on_ ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
     const int drift = hipk::launch_life_block(a, tune_, s);
     if (prof_on_) prof_launch_ += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - l0).count();
+    tune_.chain = chain_kept;
     HIP_CHECK(hipGetLastError());
     if (timed) HIP_CHECK(hipEventRecord(timed->e1, s));
     if (a.trigger && link_.bnd_n > 0) {  // the linked kernel carries the counter
@@ -741,7 +747,33 @@ class HipBackend final : public Backend {
   // profiles/r02/u8_t24*.jsonl, u8_t32.jsonl).
   // (A T = 48 pass as level-pipelined wave pairs ran no faster than T = 32,
   // the byte kernels being VALU-bound: removed in round 6, HISTORY.md.)
-  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req) const override {
+  //
+  // Life-like rules other than B3/S23 (csrc/kernels/life_rules.def) take the
+  // same window and T: their adder kernels keep four waves per SIMD at T = 12
+  // (docs/PERFORMANCE.md "Life-like rules").  Their byte kernels stop at
+  // T = 16, and they never link.
+  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule) const override {
+    KernelChoice k = choose_conway(l, rows, cols, tmax_req);
+    if (!rule_is_default(rule)) {
+      k.link = false;
+      k.tmax = std::min(k.tmax, 16);
+      if (l == Layout::U8) k.drift = false;  // no byte-layout adder variant: the DPP window
+    }
+    return k;
+  }
+  bool supports_rule(Layout l, Rule rule) const override {
+    if (rule_is_default(rule)) return true;
+    return hipk::life_block_has_rule(rule) && !(l == Layout::U8 && tune_.u8_lds);
+  }
+  std::string unsupported_rule(Layout l, Rule rule) const override {
+    if (l == Layout::U8 && tune_.u8_lds && hipk::life_block_has_rule(rule))
+      return "rule " + rule_string(rule) + ": the LDS-tiled byte kernels (tuning u8_kernel=lds) run B3/S23 only";
+    std::string have = "B3/S23";
+    for (const Rule r : hipk::life_block_rules()) have += ", " + rule_string(r);
+    return "rule " + rule_string(rule) + " is not compiled for the HIP engine (compiled: " + have +
+           "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)";
+  }
+  KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req) const {
     KernelChoice k{tmax_req > 0 ? tmax_req : preferred_tmax(l), false};
     if (l == Layout::U8 && tmax_req <= 0 && !tune_.u8_lds) {
       const int64_t strips = ceil_div(cols + 32 * 16, 62 * 32);
@@ -1090,6 +1122,8 @@ class HipBackend final : public Backend {
 };
 
 }  // namespace
+
+std::vector<Rule> hip_rules() { return hipk::life_block_rules(); }
 
 bool hip_available() {
   int n = 0;

@@ -158,6 +158,9 @@ PYBIND11_MODULE(_gol, m) {
       .def("device", &Backend::device)
       .def("stream", [](const Backend& b) { return reinterpret_cast<std::uintptr_t>(b.stream()); })
       .def("synchronize", &Backend::synchronize, py::call_guard<py::gil_scoped_release>())
+      .def("supports_rule", [](const Backend& b, Layout l, const std::string& rule) {
+        return b.supports_rule(l, parse_rule(rule));
+      })
       .def("bind_thread", &Backend::bind_thread);
   m.def("cpu_backend",
         [](int threads, int drift, std::optional<Tuning> tune) {
@@ -170,6 +173,19 @@ PYBIND11_MODULE(_gol, m) {
         },
         py::arg("device") = 0, py::arg("tune") = py::none());
   m.def("hip_available", &hip_available);
+  // Life-like rules (common.hpp): canonical text of a rule given by name or in
+  // B/S notation, the named rules, and the rules compiled for the HIP engine.
+  m.def("parse_rule", [](const std::string& s) { return rule_string(parse_rule(s)); });
+  m.def("rule_names", []() {
+    py::dict d;
+    for (const RuleName& n : kRuleNames) d[n.name] = rule_string(n.rule);
+    return d;
+  });
+  m.def("hip_rules", []() {
+    std::vector<std::string> v{rule_string(Rule{})};
+    for (const Rule r : hip_rules()) v.push_back(rule_string(r));
+    return v;
+  });
   m.def("hip_pci_bus_id", &hip_pci_bus_id);
   m.def("hip_release_errors", &hip_release_errors);
   m.def("hip_uuid", &hip_uuid);
@@ -236,6 +252,8 @@ PYBIND11_MODULE(_gol, m) {
       .def_readwrite("W", &EngineConfig::W)
       .def_readwrite("H", &EngineConfig::H)
       .def_readwrite("layout", &EngineConfig::layout)
+      .def_property("rule", [](const EngineConfig& c) { return rule_string(c.rule); },
+                    [](EngineConfig& c, const std::string& s) { c.rule = parse_rule(s); })
       .def_readwrite("decomp", &EngineConfig::decomp)
       .def_readwrite("gen_limit", &EngineConfig::gen_limit)
       .def_readwrite("check_similarity", &EngineConfig::check_similarity)
@@ -412,23 +430,61 @@ PYBIND11_MODULE(_gol, m) {
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",
         [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, int64_t gen_limit,
-           bool check_similarity, int sim_freq, int threads) {
+           bool check_similarity, int sim_freq, int threads, const std::string& rule) {
           GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
           int64_t H = a.shape(0), W = a.shape(1);
           std::vector<uint8_t> g(a.data(), a.data() + W * H);
+          const Rule rl = parse_rule(rule);
           RefResult r;
           {
             py::gil_scoped_release rel;
-            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads);
+            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl);
           }
           return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W));
         },
         py::arg("grid"), py::arg("gen_limit") = 1000, py::arg("check_similarity") = true,
-        py::arg("sim_freq") = 3, py::arg("threads") = 1);
+        py::arg("sim_freq") = 3, py::arg("threads") = 1, py::arg("rule") = "B3/S23");
 
   // ---- bitop3 / rule emulation (for kernel-level tests) ----
   m.def("rule_words", [](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2,
                          uint32_t c0, uint32_t c1, uint32_t c2) {
     return rule_host(hsum_host(a0, a1, a2), hsum_host(b0, b1, b2), hsum_host(c0, c1, c2), b1);
+  });
+  // The same through the general form (rule_host(Rule, ...)), any rule.
+  m.def("rule_words_for", [](const std::string& rule, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1,
+                             uint32_t b2, uint32_t c0, uint32_t c1, uint32_t c2) {
+    return rule_host(parse_rule(rule), hsum_host(a0, a1, a2), hsum_host(b0, b1, b2), hsum_host(c0, c1, c2), b1);
+  });
+  // Exhaustive check of the table derivation (rule_tables): the general host
+  // form on all 512 3x3 neighbourhoods (packed one per bit into 16 words) for
+  // every rule without B0, against the plain definition.  Returns
+  // (rules checked, disagreeing (rule, neighbourhood) pairs).
+  m.def("rule_tables_check", []() {
+    py::gil_scoped_release rel;
+    uint32_t plane[9][16] = {};
+    for (int i = 0; i < 512; ++i)
+      for (int k = 0; k < 9; ++k)
+        if ((i >> k) & 1) plane[k][i / 32] |= 1u << (i % 32);
+    HSum hs[3][16];
+    for (int r = 0; r < 3; ++r)
+      for (int w = 0; w < 16; ++w)
+        hs[r][w] = {bop3_host<tt::XOR3>(plane[3 * r][w], plane[3 * r + 1][w], plane[3 * r + 2][w]),
+                    bop3_host<tt::MAJ>(plane[3 * r][w], plane[3 * r + 1][w], plane[3 * r + 2][w])};
+    int64_t rules = 0, bad = 0;
+    for (unsigned b = 0; b < 512; b += 2)  // no B0
+      for (unsigned s = 0; s < 512; ++s) {
+        const Rule rule{uint16_t(b), uint16_t(s)};
+        ++rules;
+        for (int w = 0; w < 16; ++w) {
+          const uint32_t got = rule_host(rule, hs[0][w], hs[1][w], hs[2][w], plane[4][w]);
+          uint32_t want = 0;
+          for (int j = 0; j < 32; ++j) {
+            const int i = 32 * w + j, ctr = (i >> 4) & 1, n = __builtin_popcount(unsigned(i)) - ctr;
+            want |= uint32_t(((ctr ? s : b) >> n) & 1u) << j;
+          }
+          bad += __builtin_popcount(got ^ want);
+        }
+      }
+    return std::make_pair(rules, bad);
   });
 }

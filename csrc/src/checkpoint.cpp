@@ -132,7 +132,9 @@ void checkpoint_commit(const std::string& dir, const std::string& grid_path, Che
     << ",\n \"generation\": " << m.generation << ",\n \"sim_phase\": " << m.sim_phase
     << ",\n \"gen_limit\": " << m.gen_limit << ",\n \"check_similarity\": "
     << (m.check_similarity ? "true" : "false") << ",\n \"sim_freq\": " << m.sim_freq << ",\n \"layout\": \""
-    << m.layout << "\",\n \"grid\": \"" << m.grid << "\"\n}";
+    << m.layout << "\",";
+  if (!rule_is_default(parse_rule(m.rule))) o << "\n \"rule\": \"" << rule_string(parse_rule(m.rule)) << "\",";
+  o << "\n \"grid\": \"" << m.grid << "\"\n}";
   const std::string tmp = dir + "/meta.json.tmp", fin = dir + "/meta.json";
   {
     std::ofstream f(tmp, std::ios::trunc);
@@ -180,6 +182,8 @@ CheckpointMeta checkpoint_load(const std::string& dir) {
   m.check_similarity = cs == "true";
   const std::string lay = json_field(js, "layout");
   if (!lay.empty()) m.layout = lay;
+  const std::string rule = json_field(js, "rule");
+  if (!rule.empty()) m.rule = rule_string(parse_rule(rule));
   const std::string grid = json_field(js, "grid");
   if (!grid.empty()) {
     GOL_REQUIRE(checkpoint_grid_name_ok(grid), "checkpoint '" + dir + "': bad grid file name '" + grid +

@@ -9,8 +9,9 @@
 namespace gol {
 
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
-                            bool check_similarity, int sim_freq, int threads) {
+                            bool check_similarity, int sim_freq, int threads, Rule rule) {
   GOL_REQUIRE(int64_t(grid.size()) == W * H, "grid size mismatch");
+  require_no_b0(rule, rule_string(rule));
   GOL_REQUIRE(sim_freq > 0, "similarity frequency must be positive");
   std::vector<uint8_t> a(grid.size()), b(grid.size());
   for (size_t i = 0; i < grid.size(); ++i) a[i] = uint8_t(grid[i] == 1 || grid[i] == '1');
@@ -49,7 +50,7 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
         for (int64_t x = 0; x < W; ++x) {
           int64_t xl = x == 0 ? W - 1 : x - 1, xr = x == W - 1 ? 0 : x + 1;
           int s = up[xl] + up[x] + up[xr] + mid[xl] + mid[xr] + dn[xl] + dn[x] + dn[xr];
-          n[y * W + x] = uint8_t(s == 3 || (s == 2 && mid[x]));
+          n[y * W + x] = uint8_t(((mid[x] ? rule.survive : rule.birth) >> s) & 1u);
         }
       }
     });

@@ -35,6 +35,8 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   GOL_REQUIRE(cfg_.W > 0 && cfg_.H > 0, "grid dimensions must be positive");
   GOL_REQUIRE(cfg_.sim_freq > 0, "similarity frequency must be positive");
   GOL_REQUIRE(cfg_.gen_limit >= 0, "generation limit must be >= 0");
+  GOL_REQUIRE(cfg_.rule.birth < 512 && cfg_.rule.survive < 512, "rule: neighbour counts are 0..8");
+  require_no_b0(cfg_.rule, rule_string(cfg_.rule));
   rank_ = tr_->rank();
   if (cfg_.overlap == 1) cfg_.overlap = 3;  // "on" is the trigger schedule
   int64_t unit = (cfg_.layout == Layout::Bits || cfg_.W % 32 == 0) ? 32 : 1;
@@ -53,11 +55,12 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Layout the temporal blocks run on.
   const Layout cl = via_bits_ ? Layout::Bits : cfg_.layout;
+  if (!be_->supports_rule(cl, cfg_.rule)) fail(be_->unsupported_rule(cl, cfg_.rule));
   // Every rank must take the same decision (a drifting frame or a schedule
   // that moves a halo exchange is only consistent in lockstep), so it is
   // made for the smallest tile of the decomposition, not this rank's.
   const Backend::KernelChoice kc =
-      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax);
+      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule);
   tmax_ = std::min(kc.tmax, cl == Layout::U8 ? 32 : 16);
   // Epoch depth: a deeper halo means fewer latency-bound exchanges (or local
   // periodic fills: two ~5 us launches each) but ~D redundant rows per epoch.
@@ -572,6 +575,7 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
   a.row_lo = row_lo;
   a.row_hi = row_hi;
   a.T = T;
+  a.rule = cfg_.rule;
   a.gen_base = gen_base;
   if (capturing_) {
     // Replayable: the flags offset comes from gen_dev_ at run time.

@@ -57,6 +57,8 @@ struct Options {
   std::string input;
   std::string engine = "auto";  // auto | hip | cpu | ref
   std::string layout = "auto";  // auto | bits | u8
+  Rule rule;                    // --rule (default B3/S23)
+  bool rule_set = false;
   std::string decomp = "auto";
   std::string comm = "auto";  // auto | thread | rccl (in-process ranks)
   std::string output;  // default: the matching reference build's file (see default_output)
@@ -88,6 +90,10 @@ struct Options {
                "  --layout auto|bits|u8       cell storage (bits needs width %% 32 == 0)\n"
                "  --u8-compute auto|bits|bytes  byte-layout epochs on bit words (packed once per\n"
                "                              epoch; auto: on the GPU) or on the bytes themselves\n"
+               "  --rule NAME|B../S..         Life-like rule: B<digits>/S<digits> (e.g. B36/S23) or a name:\n"
+               "                              life, highlife, daynight, seeds, replicator, lwod, 34life\n"
+               "                              (default B3/S23; no B0; the hip engine runs the named ones,\n"
+               "                              the cpu and ref engines any)\n"
                "  --gens N                    GEN_LIMIT (default 1000)\n"
                "  --sim-freq F                SIMILARITY_FREQUENCY (default 3)\n"
                "  --no-similarity             disable the similarity check\n"
@@ -139,6 +145,7 @@ Options parse(int argc, char** argv) {
       if (v != "auto" && v != "bits" && v != "bytes") usage(2);
       o.u8_compute = v == "bits" ? 1 : v == "bytes" ? 0 : -1;
     }
+    else if (a == "--rule") o.rule = parse_rule(next()), o.rule_set = true;
     else if (a == "--decomp") o.decomp = next();
     else if (a == "--comm") o.comm = next();
     else if (a == "--gens") o.gens = std::atoll(next().c_str()), o.gens_set = true;
@@ -196,6 +203,12 @@ Options parse(int argc, char** argv) {
     if ((o.W > 0 && o.W != m.W) || (o.H > 0 && o.H != m.H))
       throw Error("--resume: checkpoint is " + std::to_string(m.W) + "x" + std::to_string(m.H) +
                   ", not the requested " + std::to_string(o.W) + "x" + std::to_string(o.H));
+    // The rule is the checkpoint's; a different explicit --rule would continue
+    // another automaton from this grid under the old generation count.
+    const Rule ck_rule = parse_rule(m.rule);
+    if (o.rule_set && o.rule != ck_rule)
+      throw Error("--resume: checkpoint was taken with --rule " + m.rule + ", not " + rule_string(o.rule));
+    o.rule = ck_rule;
     o.W = m.W;
     o.H = m.H;
     o.input = checkpoint_grid_path(o.resume);
@@ -273,7 +286,7 @@ int run(const Options& o) {
       read_text_grid(o.input, o.W, o.H, grid);
     }
     read_ms = ms_since(t0);
-    RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads);
+    RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule);
     res.generations = rr.generations;
     res.loop_ms = rr.loop_ms;
     res.executed = rr.generations;
@@ -289,6 +302,7 @@ int run(const Options& o) {
     cfg.W = o.W;
     cfg.H = o.H;
     cfg.layout = layout;
+    cfg.rule = o.rule;
     cfg.decomp = o.decomp;
     cfg.gen_limit = o.gens;
     cfg.check_similarity = o.similarity;
@@ -443,6 +457,7 @@ int run(const Options& o) {
         m.check_similarity = o.similarity;
         m.sim_freq = o.sim_freq;
         m.layout = layout_name(layout);
+        m.rule = rule_string(o.rule);
         // Fault injection (tests): die after the N-th checkpoint's tiles are
         // written, before it is committed.
         if (const int c = o.tune.i("fault_checkpoint_crash"))
@@ -482,7 +497,8 @@ int run(const Options& o) {
         tuning_changed += (tuning_changed.size() > 1 ? ", " : "") + jstr(kv.first) + ": " + jstr(kv.second);
       tuning_changed += "}";
       f << "{\"engine\": " << jstr(engine) << ", \"backend\": " << jstr(backends[0]->name())
-        << ", \"layout\": " << jstr(layout_name(layout)) << ", \"ranks\": " << P
+        << ", \"layout\": " << jstr(layout_name(layout)) << ", \"rule\": " << jstr(rule_string(o.rule))
+        << ", \"ranks\": " << P
         << ", \"decomp\": " << jstr(engines[0]->decomp().describe()) << ", \"tuning\": " << jstr(o.tune.summary())
         << ", \"tuning_changed\": " << tuning_changed << ", \"W\": " << o.W
         << ", \"H\": " << o.H << ", \"generations\": " << res.generations

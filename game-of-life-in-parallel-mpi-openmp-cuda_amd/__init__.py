@@ -10,11 +10,22 @@ per GPU.
 Import as ``gol_amd`` (symlink to this directory).
 """
 from ._native import hip_available, native
-from .models.life import LifeConfig, RunReport, Simulation, make_backend, reference_run, simulate
+from .models.life import LifeConfig, RunReport, Simulation, make_backend, parse_rule, reference_run, simulate
 from .ops.life_ops import life_step, life_step_numpy, life_step_torch, random_grid
 
 __version__ = "0.1.0"
 
+
+def __getattr__(name):
+    # RULES: the named Life-like rules, name -> canonical B/S text (read from
+    # the native module on first use, so importing the package stays cheap).
+    if name == "RULES":
+        rules = dict(native().rule_names())
+        globals()["RULES"] = rules
+        return rules
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = ["LifeConfig", "RunReport", "Simulation", "make_backend", "reference_run", "simulate",
            "life_step", "life_step_numpy", "life_step_torch", "random_grid", "native",
-           "hip_available", "__version__"]
+           "hip_available", "parse_rule", "RULES", "__version__"]

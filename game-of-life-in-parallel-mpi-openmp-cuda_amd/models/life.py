@@ -37,6 +37,7 @@ class LifeConfig:
     check_similarity: bool = True
     sim_freq: int = 3
     layout: str = "auto"        # auto | bits | u8
+    rule: str = "B3/S23"        # Life-like rule: B<digits>/S<digits> or a name of gol_amd.RULES (no B0)
     decomp: str = "auto"        # auto | PxQ
     tmax: int = 0               # generations per kernel launch (0 = the backend's choice: bits 12 adder /
                                 # 16 DPP; u8 32 / 24 / 16 by tile size)
@@ -71,6 +72,7 @@ class LifeConfig:
         c.W = int(self.width)
         c.H = int(self.height)
         c.layout = C.Layout.Bits if self.resolved_layout() == "bits" else C.Layout.U8
+        c.rule = str(self.rule)
         c.decomp = self.decomp
         c.gen_limit = int(self.gen_limit)
         c.check_similarity = bool(self.check_similarity)
@@ -89,6 +91,16 @@ class LifeConfig:
         c.u8_compute = {"auto": -1, "bytes": 0, "bits": 1}[self.u8_compute]
         c.tune = make_tuning(self.tune)
         return c
+
+
+DEFAULT_RULE = "B3/S23"
+
+
+def parse_rule(rule: str) -> str:
+    """Canonical ``B<digits>/S<digits>`` text of a Life-like rule given in B/S
+    notation (case-insensitive, slash optional) or by a name of ``RULES``.
+    Raises on malformed text, digit 9, repeated digits and B0."""
+    return native().parse_rule(str(rule))
 
 
 def make_tuning(tune=None):
@@ -231,7 +243,7 @@ class Simulation:
         d = self._eng.decomp
         g = self._eng.compute_geom  # the tile the temporal blocks run on (halos)
         return {"backend": self.backend.name(), "transport": self.transport.name(),
-                "layout": self.config.resolved_layout(), "decomp": d.describe(),
+                "layout": self.config.resolved_layout(), "rule": self._eng.config.rule, "decomp": d.describe(),
                 "rank": self.rank, "ranks": d.nranks(), "tile_rows": g.H, "tile_cols": g.W,
                 "halo_rows": g.Dv, "halo_words": g.hw, "tmax": self._eng.tmax,
                 "epoch": self._eng.epoch_depth, "pitch": self._eng.geom.pitch, "overlap": self._eng.overlap(),
@@ -278,6 +290,8 @@ class Simulation:
             parts.append("byte grid packed to bit words once per run" if e.via_bits else "byte-layout kernels")
         if e.row_ring:
             parts.append("row ring (no halo fills)")
+        if e.config.rule != DEFAULT_RULE:
+            parts.append(f"rule {e.config.rule}")
         return ", ".join(parts)
 
     # -- state -----------------------------------------------------------
@@ -343,10 +357,11 @@ def simulate(grid: np.ndarray, gens: int, engine: str = "auto", layout: str = "a
 
 
 def reference_run(grid: np.ndarray, gen_limit: int = 1000, check_similarity: bool = True,
-                  sim_freq: int = 3, threads: int = 1) -> tuple[np.ndarray, int, float]:
-    """Exact eager serial loop of src/game.c (native).  Returns (grid, gens, ms)."""
+                  sim_freq: int = 3, threads: int = 1, rule: str = DEFAULT_RULE) -> tuple[np.ndarray, int, float]:
+    """Exact eager serial loop of src/game.c (native), under any Life-like
+    ``rule`` without B0.  Returns (grid, gens, ms)."""
     gens, ms, out = native().cpu_reference_run(np.ascontiguousarray(grid, dtype=np.uint8), int(gen_limit),
-                                               bool(check_similarity), int(sim_freq), int(threads))
+                                               bool(check_similarity), int(sim_freq), int(threads), str(rule))
     return out, int(gens), float(ms)
 
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import concurrent.futures as cf
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -40,8 +41,15 @@ HOST_SRCS = ["src/decomp.cpp", "src/parallel.cpp", "src/backend_cpu.cpp", "src/t
 # (docs/HISTORY.md) and their numbers in docs/HISTORY.md / PERFORMANCE.md.
 LIFE_VARIANTS = ["bits_w1_dpp", "bits_w1_add", "u8_w1_dpp", "u8_w1_add",
                  *[f"u8_w1_dpp_t{t}" for t in (24, 32)]]  # deep byte passes
+# Life-like rules besides B3/S23: the names of csrc/kernels/life_rules.def,
+# three one-line translation units each (bit layout with the DPP and the
+# adder window, byte layout with the DPP window).
+RULES_DEF = CSRC / "kernels" / "life_rules.def"
+RULE_NAMES = re.findall(r"^GOL_RULE\((\w+),", RULES_DEF.read_text(), flags=re.M)
+RULE_VARIANTS = [f"{n}_{v}" for n in RULE_NAMES for v in ("bits_dpp", "bits_add", "u8_dpp")]
 HIP_SRCS = ["src/backend_hip.hip", "src/transport_rccl.hip", "kernels/life_block.hip",
-            *[f"kernels/life_block_{v}.hip" for v in LIFE_VARIANTS], "kernels/life_step_lds.hip",
+            *[f"kernels/life_block_{v}.hip" for v in LIFE_VARIANTS],
+            *[f"kernels/life_rule_{v}.hip" for v in RULE_VARIANTS], "kernels/life_step_lds.hip",
             "kernels/tile_ops.hip"]
 BIND_SRCS = ["src/bindings.cpp"]
 CLI_MAIN = "tools/gol_main.cpp"
@@ -61,7 +69,7 @@ def _hipcc() -> str:
 
 def _headers_mtime() -> float:
     m = 0.0
-    for p in list(CSRC.rglob("*.hpp")) + list(CSRC.rglob("*.h")):
+    for p in list(CSRC.rglob("*.hpp")) + list(CSRC.rglob("*.h")) + list(CSRC.rglob("*.def")):
         m = max(m, p.stat().st_mtime)
     return m
 
@@ -70,7 +78,7 @@ def _compile_cmd(src: Path, obj: Path) -> list[str]:
     inc = [f"-I{CSRC / 'include'}", f"-I{CSRC}"]
     if src.suffix == ".hip":
         extra = []
-        if src.name.startswith("life_block_"):
+        if src.name.startswith(("life_block_", "life_rule_")):
             # Scheduler for the temporal-blocking kernels: max-ILP interleaves the
             # independent generation levels.  Measured on MI355X it is on par
             # with the default strategy (the kernel is VALU-throughput bound);
@@ -95,7 +103,7 @@ def _deps(obj: Path) -> list[Path] | None:
         return None
     text = d.read_text().replace("\\\n", " ")
     _, _, rest = text.partition(":")
-    return [Path(t) for t in rest.split() if t.endswith((".hpp", ".h", ".hip", ".inc"))]
+    return [Path(t) for t in rest.split() if t.endswith((".hpp", ".h", ".hip", ".inc", ".def"))]
 
 
 def _needs(obj: Path, src: Path, hdr_mtime: float) -> bool:
@@ -129,7 +137,7 @@ def build(verbose: bool = False, jobs: int | None = None, force: bool = False) -
     # Longest compiles first (deep byte passes, then the kernel variants), so
     # the pool does not end on one long translation unit.
     todo.sort(key=lambda s: 0 if any(f"_t{t}" in s for t in (24, 32, 48, 64)) else
-              1 if "life_block_" in s else 2)
+              1 if "life_block_" in s or "life_rule_" in s else 2)
     jobs = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = [ex.submit(_run, _compile_cmd(CSRC / s, objs[s]), verbose) for s in todo]

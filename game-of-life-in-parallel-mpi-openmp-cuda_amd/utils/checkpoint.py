@@ -25,7 +25,7 @@ import re
 from pathlib import Path
 from typing import Optional
 
-from ..models.life import LifeConfig, RunReport, Simulation
+from ..models.life import DEFAULT_RULE, LifeConfig, RunReport, Simulation, parse_rule
 from .termination import reported_generations, sim_phase_at
 
 
@@ -91,6 +91,11 @@ def save_checkpoint(sim: Simulation, directory: str, is_root: bool = True, barri
         "gen_limit": cfg.gen_limit, "check_similarity": cfg.check_similarity,
         "sim_freq": cfg.sim_freq, "layout": cfg.resolved_layout(), "grid": name,
     }
+    # "rule" only when it is not the default: checkpoints of B3/S23 runs stay
+    # byte for byte what they were (a missing key means B3/S23).
+    rule = parse_rule(cfg.rule)
+    if rule != DEFAULT_RULE:
+        meta = {k: v for k, v in meta.items() if k != "grid"} | {"rule": rule, "grid": name}
     grid = d / name
     if is_root:
         from .io import create_text_file  # noqa: PLC0415
@@ -134,7 +139,7 @@ def load_checkpoint(directory: str, **overrides) -> tuple[LifeConfig, Path]:
     cfg = LifeConfig(meta["width"], meta["height"], gen_limit=meta["gen_limit"],
                      check_similarity=meta["check_similarity"], sim_freq=meta["sim_freq"],
                      layout=meta.get("layout", "auto"), start_gen=meta["generation"],
-                     sim_phase=meta["sim_phase"])
+                     sim_phase=meta["sim_phase"], rule=parse_rule(meta.get("rule", DEFAULT_RULE)))
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg, d / _meta_grid(meta, d)

@@ -25,7 +25,11 @@ def main() -> None:
            "`python -m gol_amd.cli`, bench.py) or `LifeConfig(tune={key: value})`; its `GOL_*` variable",
            "overrides the default (precedence: default < environment < explicit). Backends, the engine and",
            "the transports read the table once, at construction. The kernel variants and schedules measured",
-           "slower than the defaults were removed in round 6 (their numbers: docs/HISTORY.md).", ""]
+           "slower than the defaults were removed in round 6 (their numbers: docs/HISTORY.md).", "",
+           "Life-like rules other than B3/S23 (`--rule`, `LifeConfig(rule=)`) run kernels that are never linked",
+           "or chained: `link=1` and `chain=1` are ignored for them, the `u8` adder request (`xlane=3`) runs",
+           "the DPP window, their byte kernels stop at `tmax` 16, and `u8_kernel=lds` is refused.",
+           ""]
     for c, title in CLASSES.items():
         out += [f"## {c}: {title}", "", "| key | environment | default | meaning |", "|---|---|---|---|"]
         for k in keys:
