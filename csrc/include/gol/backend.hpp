@@ -156,6 +156,29 @@ class Backend {
                                      Rule /*rule*/ = Rule{}) const {
     return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l)};
   }
+  // Quiet-tile skipping (BlockArgs::quiet, gol/quiet.hpp).  quiet_mode(): the
+  // backend's tuning quiet_skip (0: it has no such kernel or it is off, 1
+  // every eligible block, -1 the engine's auto policy) and the policy's
+  // parameters; quiet_block(): generations per block of that kernel.
+  // quiet_invalidate(): something other than run_block wrote (or may write)
+  // a grid buffer, so the next skipping block must recompute every tile.
+  // quiet_report(): the newest finished skipping-kernel launch - its number
+  // (counting from 1), its tiles and how many of them were clean after it -
+  // and the tiles skipped by all launches so far; false before the first.
+  struct QuietTuning {
+    int mode = 0, scout = 128, on = 60, off = 35;
+  };
+  virtual QuietTuning quiet_mode() const { return {}; }
+  virtual int quiet_block() const { return 0; }
+  virtual void quiet_invalidate() {}
+  // Allocates what skipping blocks on tile g need, before the first run.
+  virtual void quiet_prepare(const TileGeom& /*g*/) {}
+  virtual bool quiet_report(int64_t* /*seq*/, int64_t* /*tiles*/, int64_t* /*clean*/, int64_t* /*skipped_total*/) {
+    return false;
+  }
+  // Waves per tile of the skipping kernel, and tiles launched by it so far.
+  virtual int quiet_tile_waves() const { return 0; }
+  virtual int64_t quiet_tiles_launched() const { return 0; }
   // Whether run_block evaluates `rule` (BlockArgs::rule) on tiles of this
   // layout.  The CPU backend runs any rule without B0; the HIP backend the
   // rules compiled from csrc/kernels/life_rules.def.  unsupported_rule() is

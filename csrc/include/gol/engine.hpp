@@ -22,6 +22,7 @@
 
 #include "gol/backend.hpp"
 #include "gol/decomp.hpp"
+#include "gol/quiet.hpp"
 #include "gol/tile.hpp"
 #include "gol/transport.hpp"
 
@@ -180,8 +181,20 @@ class Engine {
   // The byte (or bit) tile's current buffer, brought up to date first.
   void* current_buffer() {
     sync_bytes();
+    be_->quiet_invalidate();  // the caller may write through the pointer
     return buf_[cur_];
   }
+  // Quiet-tile skipping (gol/quiet.hpp; tuning quiet_skip): "off" | "on" |
+  // "auto:dense" | "auto:skipping"; T-generation blocks run by the dense
+  // kernels, as detecting scouts and by the skipping kernel in skipping mode;
+  // waves the skipping kernel launched and how many of them skipped their
+  // tile (complete once a run has returned).
+  std::string quiet_mode() const { return quiet_.name(); }
+  int64_t quiet_blocks_dense() const { return quiet_.blocks_dense; }
+  int64_t quiet_blocks_scout() const { return quiet_.blocks_scout; }
+  int64_t quiet_blocks_skip() const { return quiet_.blocks_skip; }
+  int64_t quiet_waves_launched() const { return be_->quiet_tiles_launched() * be_->quiet_tile_waves(); }
+  int64_t quiet_waves_skipped();
   // Storage-frame drift (cells, mod W) left by drifting kernels
   // (Backend::drifts): stored column x holds true column x - drift.
   int64_t drift() const { return drift_; }
@@ -325,6 +338,11 @@ class Engine {
   bool poll_copy_side_ = true;  // tuning poll_copy_side: single-rank polls on Backend::poll_side()
   int64_t drift_ = 0;
   int64_t graph_drift_[4] = {0, 0, 0, 0};
+  // Quiet-tile skipping: the policy (mode 0 where the tile is not eligible),
+  // and the last report read from the backend.
+  quiet::Policy quiet_;
+  int64_t quiet_seq_seen_ = 0, quiet_skipped_tiles_ = 0;
+  void quiet_poll();
   // Overlap auto trial.
   bool auto_overlap_ = false;       // trial still running
   bool auto_decided_ = false;

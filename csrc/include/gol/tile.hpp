@@ -106,6 +106,11 @@ struct BlockArgs {
   // light cone of the boundary rows the epoch will send) run at top issue
   // priority, nothing counted - so the boundary region leads the interior.
   bool hot = false;
+  // Quiet-tile skipping (gol/quiet.hpp): the backend may run its detecting /
+  // skipping kernel, whose workgroups leave a tile alone when it and its
+  // light cone are what they were T generations ago.  Results are the same
+  // either way; a backend without such a kernel ignores it.
+  bool quiet = false;
 };
 
 }  // namespace gol

@@ -140,6 +140,13 @@ int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t st
   // engine allows that only for whole-width tiles of 32-cell words, and the
   // left halo must hold the 2T cells its one-sided light cone consumes (wrap
   // mode reads the wrapped owned words instead).
+  // Quiet-tile skipping (BlockArgs::quiet): the detecting / skipping kernel
+  // where the block can be planned for it; else the kernels below, and the
+  // next skipping launch finds no words to read.
+  if (tune.quiet) {
+    if (a.quiet && !rk && g.layout == Layout::Bits && launch_bits_w1_dpp_quiet(p, rows, a.T, tune, stream)) return 0;
+    tune.quiet->prev.T = 0;
+  }
   if (x == kXlaneAuto) x = kXlaneAdd;  // the engine decided through allow_drift
   // The one-sided window also consumes 2T cells of its wave's single halo
   // word per pass, so passes deeper than 16 (the byte layout's T = 24 / 32)

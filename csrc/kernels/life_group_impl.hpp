@@ -265,9 +265,10 @@ struct Prio {
 // 0-2 steps of its classic end that do not fill a 3-step loop iteration) and
 // stops there.  One code path for both kinds of wave: a separate remainder
 // branch beside the epilogue made hipcc allocate 199 instead of 123 VGPRs.
-template <int T, class IO, int E, int S>
+// WR: Writer<IO>, or any sink with row(r, v) (life_quiet_impl.hpp).
+template <int T, class IO, int E, int S, class WR>
 __device__ __forceinline__ void epilogue_tri(Levels<T, IO::W>& st, RowReader<IO>& rd, const uint32_t* below,
-                                             int lane, const Writer<IO>& wr, int k, int nfull, Prio& prio) {
+                                             int lane, WR& wr, int k, int nfull, Prio& prio) {
   if constexpr (E < 2 * T) {
     if (E >= nfull) return;  // wave-uniform
     prio.at(prio.done0 + epi_work_before<T>(E));

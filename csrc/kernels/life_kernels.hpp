@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "gol/quiet.hpp"
 #include "gol/tile.hpp"
 
 namespace gol {
@@ -91,6 +92,19 @@ struct LifeBlockParams {
   // rounds (~3.4 us each) before publishing, so a missing dependency wait
   // reads stale rows deterministically instead of by chance.
   int fault_delay;
+  // Quiet-tile skipping (life_quiet_kernel, gol/quiet.hpp): one word per
+  // (strip, group) tile.  quiet_prev: the previous block's words (null:
+  // nothing may skip); quiet_next: this block's.  The counters at quiet_count
+  // (kQuietCountBytes, below) pack, per launch, groups done (bits 0..19),
+  // clean tiles (20..39) and skipped groups (40..59); the last group to finish
+  // stores quiet_seq << 40 | clean << 20 | skipped to quiet_report[0]
+  // (host-mapped) and resets them; quiet_report[1]: tiles skipped by all
+  // launches so far.
+  const uint32_t* quiet_prev;
+  uint32_t* quiet_next;
+  unsigned long long* quiet_count;
+  unsigned long long* quiet_report;
+  uint32_t quiet_seq;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -177,8 +191,22 @@ inline void link_join(LinkState& L) {
   L.prev_valid = false;
 }
 
+// Backend-owned state of the quiet-tile skipping kernel (BlockArgs::quiet;
+// gol/quiet.hpp): the two tile-word maps consecutive blocks alternate over,
+// and what the last skipping-kernel launch was (quiet::may_follow).
+struct QuietState {
+  quiet::Launch prev{};            // prev.T == 0: no words to read
+  int cur = 0;                     // map the last launch wrote
+  uint32_t seq = 0;                // launches so far (24 bits reach the report)
+  int64_t tiles = 0;               // tiles of the last launch
+  unsigned long long* report = nullptr;       // host-mapped report word (device alias)
+  const unsigned long long* report_host = nullptr;
+  int seg_rows = 96;               // output rows per group the plan aims at (tuning quiet_rows)
+};
+
 struct LifeTuning {
   int cus = 256;            // compute units of the device
+  QuietState* quiet = nullptr;  // quiet-tile skipping state (launch_bits_w1_dpp_quiet)
   int target_waves = 0;     // waves per launch round (0 = occupancy x CUs x 4 SIMDs)
   int min_seg_rows = 16;    // lower bound on rows per wave segment
   int xlane = kXlaneAuto;   // cross-lane primitive
@@ -226,6 +254,19 @@ GOL_LIFE_VARIANT(launch_bits_w1_dpp);
 GOL_LIFE_VARIANT(launch_u8_w1_dpp);
 GOL_LIFE_VARIANT(launch_bits_w1_add);
 GOL_LIFE_VARIANT(launch_u8_w1_add);
+// The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave
+// groups of short segments; life_block_bits_w1_dpp_quiet.hip): wrap-mode
+// blocks over a row ring's owned rows only.  Returns false (nothing
+// launched) where the block cannot be planned that way.
+bool launch_bits_w1_dpp_quiet(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune, hipStream_t s);
+void prepare_bits_w1_dpp_quiet(const LifeTuning& tune, int64_t H, int64_t words);
+constexpr int kQuietT = 12;
+// LifeBlockParams::quiet_count, in 64-bit words a cache line apart: the
+// launch's counter, the tiles skipped by all launches, kQuietCounters
+// first-level counters.
+constexpr unsigned kQuietCounters = 64;
+constexpr int kQuietCountStride = 16;
+constexpr size_t kQuietCountBytes = size_t(2 + kQuietCounters) * kQuietCountStride * 8;
 
 // Single-generation LDS-tiled byte-layout kernel (life_step_lds.hip).
 void launch_life_step_lds(const BlockArgs& a, int lds_rows, bool wrap, hipStream_t stream);

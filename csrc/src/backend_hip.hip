@@ -145,7 +145,8 @@ class HipBackend final : public Backend {
         if (which != 1) HIP_CHECK(hipMemsetAsync(buf, 0, n, stream_));  // ordered before the launch on stream_
         cap = n;
       }
-      if (check_dev_) check_ptr(buf, which == 0 ? "chain flags" : which == 1 ? "chain slots" : "link words");
+      if (check_dev_)
+        check_ptr(buf, which == 0 ? "chain flags" : which == 1 ? "chain slots" : which < 5 ? "link words" : "quiet words");
       return static_cast<uint32_t*>(buf);
     };
     if (split_trace(t.s("wg_trace"), &trace_at_, &trace_path_)) {
@@ -158,10 +159,20 @@ class HipBackend final : public Backend {
     }
     // Kernel error word: fine-grained pinned host memory the kernels write
     // through its device alias and the host reads without a copy.
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_host_), 4 * sizeof(uint32_t), hipHostMallocMapped));
-    for (int i = 0; i < 4; ++i) err_host_[i] = 0;
+    // Words 4..7: the skipping kernel's two 64-bit report words (QuietState).
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_host_), 8 * sizeof(uint32_t), hipHostMallocMapped));
+    for (int i = 0; i < 8; ++i) err_host_[i] = 0;
     tune_.chain_spin_log2 = std::min(24, std::max(4, t.i("chain_spin")));
     HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&tune_.err), err_host_, 0));
+    // Quiet-tile skipping (tuning quiet_skip; gol/quiet.hpp).
+    quiet_tune_.mode = std::max(-1, std::min(1, t.i("quiet_skip")));
+    quiet_tune_.scout = std::max(1, t.i("quiet_scout"));
+    quiet_tune_.on = t.i("quiet_on");
+    quiet_tune_.off = std::min(t.i("quiet_off"), quiet_tune_.on);
+    quiet_.seg_rows = std::max(1, t.i("quiet_rows"));
+    quiet_.report = reinterpret_cast<unsigned long long*>(tune_.err + 4);
+    quiet_.report_host = reinterpret_cast<const unsigned long long*>(err_host_ + 4);
+    if (!cu_part_.empty()) quiet_tune_.mode = 0;
   }
   static std::atomic<int>& live_backends(int dev) {
     static std::atomic<int> n[64];
@@ -210,6 +221,33 @@ class HipBackend final : public Backend {
     }
   }
   int64_t linked_launches() const override { return link_.linked; }
+  QuietTuning quiet_mode() const override { return quiet_tune_; }
+  int quiet_block() const override { return hipk::kQuietT; }
+  void quiet_invalidate() override { quiet_.prev.T = 0; }
+  void quiet_prepare(const TileGeom& g) override {
+    if (quiet_tune_.mode == 0 || g.layout != Layout::Bits) return;
+    GOL_ON_DEVICE();
+    hipk::prepare_bits_w1_dpp_quiet(tune_, g.H, g.W / 32);
+  }
+  bool quiet_report(int64_t* seq, int64_t* tiles, int64_t* clean, int64_t* skipped_total) override {
+    if (quiet_.seq == 0) return false;
+    // Two aligned 64-bit words the device stores whole; the newest launch's
+    // words may still be on their way (the policy may lag).
+    const unsigned long long all = __atomic_load_n(quiet_.report_host + 1, __ATOMIC_ACQUIRE);
+    const unsigned long long r = __atomic_load_n(quiet_.report_host, __ATOMIC_ACQUIRE);
+    if (r == 0) return false;
+    // The report carries 24 bits of the launch number: the newest launch at
+    // or before the last one issued with those bits.
+    int64_t n = int64_t(quiet_.seq & ~0xFFFFFFu) | int64_t(r >> 40);
+    if (n > int64_t(quiet_.seq)) n -= int64_t(1) << 24;
+    *seq = n;
+    *tiles = quiet_.tiles;
+    *clean = int64_t((r >> 20) & 0xFFFFFu);
+    *skipped_total = int64_t(all);
+    return true;
+  }
+  int quiet_tile_waves() const override { return 4; }
+  int64_t quiet_tiles_launched() const override { return quiet_tiles_; }
   std::string name() const override {
     hipk::LifeTuning t = tune_;
     t.chain = chain_mode_;
@@ -601,8 +639,15 @@ class HipBackend final : public Backend {
     // Rule kernels (any rule but B3/S23) are never linked or chained, forced
     // link=1 / chain=1 included.
     const bool conway = rule_is_default(a.rule);
-    const bool linkable = conway && (link_on_ || (a.link && link_mode_ < 0)) && link_.stream[1] && !capturing &&
-                          a.g.layout == Layout::Bits;
+    // Quiet-tile skipping: stream launches on the compute stream, never
+    // linked, chained or traced; any other block leaves the next skipping
+    // launch no words to read.
+    const bool quiet = a.quiet && quiet_tune_.mode != 0 && conway && !capturing && a.g.layout == Layout::Bits &&
+                       trace_at_ < 0;
+    tune_.quiet = quiet ? &quiet_ : nullptr;
+    if (!quiet) quiet_.prev.T = 0;
+    const bool linkable = !quiet && conway && (link_on_ || (a.link && link_mode_ < 0)) && link_.stream[1] &&
+                          !capturing && a.g.layout == Layout::Bits;
     if (!linkable) join_streams();
     tune_.link = linkable ? &link_ : nullptr;
     if (chain_mode_) {  // chained groups: own stream only, never inside a graph capture
@@ -628,8 +673,9 @@ class HipBackend final : public Backend {
       link_.bnd_count = trigger_counter();
     }
     Pending* timed = nullptr;
-    if (chain_mode_ < 0 && !linkable && conway) timed = autotune_chain(a);
+    if (chain_mode_ < 0 && !linkable && conway && !quiet) timed = autotune_chain(a);
     if (linkable) tune_.chain = 0;
+    const int64_t quiet_seq0 = quiet_.seq;
     const int chain_kept = tune_.chain;
     if (!conway) tune_.chain = 0;
     if (timed) HIP_CHECK(hipEventRecord(timed->e0, s));
@@ -638,6 +684,7 @@ class HipBackend final : public Backend {
     if (prof_on_) prof_launch_ += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - l0).count();
     tune_.chain = chain_kept;
     HIP_CHECK(hipGetLastError());
+    if (quiet_.seq != quiet_seq0) quiet_tiles_ += quiet_.tiles;
     if (timed) HIP_CHECK(hipEventRecord(timed->e1, s));
     if (a.trigger && link_.bnd_n > 0) {  // the linked kernel carries the counter
       trigger_total_ += uint64_t(link_.bnd_n);
@@ -754,6 +801,12 @@ class HipBackend final : public Backend {
   // T = 16, and they never link.
   KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule) const override {
     KernelChoice k = choose_conway(l, rows, cols, tmax_req);
+    // quiet_skip=1: every block the skipping kernel's (the DPP window at its
+    // block size, never linked); the auto policy keeps the choice above and
+    // applies where that is blocks of the skipping kernel's size.
+    if (quiet_tune_.mode > 0 && rule_is_default(rule) && l == Layout::Bits && !tune_.u8_lds &&
+        (tmax_req <= 0 || tmax_req == hipk::kQuietT))
+      k = {hipk::kQuietT, false, false};
     if (!rule_is_default(rule)) {
       k.link = false;
       k.tmax = std::min(k.tmax, 16);
@@ -820,6 +873,7 @@ class HipBackend final : public Backend {
   // The LDS-tiled byte kernels read rows modulo the torus too.
   bool wraps_rows(Layout l) const override { return tune_.wrap && l == Layout::U8 && tune_.u8_lds; }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_rotate_cols(static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), g, shift, stream_);
@@ -827,6 +881,7 @@ class HipBackend final : public Backend {
   }
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t i0,
                     int64_t n) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_convert_rows(static_cast<const uint8_t*>(src), gs, static_cast<uint8_t*>(dst), gd, i0, n,
@@ -929,6 +984,7 @@ class HipBackend final : public Backend {
     }
   }
   void fill_periodic(void* buf, const TileGeom& g, bool cols, bool rows) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     auto* p = static_cast<uint8_t*>(buf);
@@ -939,6 +995,7 @@ class HipBackend final : public Backend {
     HIP_CHECK(hipGetLastError());
   }
   void fill_cols_rows(void* buf, const TileGeom& g, int64_t r0, int64_t n, void* stream) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_fill_cols_rows(static_cast<uint8_t*>(buf), g, r0, n, stream ? static_cast<hipStream_t>(stream) : stream_);
@@ -969,6 +1026,7 @@ class HipBackend final : public Backend {
   // Host <-> tile transfers go through a bounded device staging buffer so a
   // 32768^2 (1 GiB) or larger grid never needs a second full-size copy.
   void load_owned(void* buf, const TileGeom& g, const uint8_t* cells, int64_t ld) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     const int64_t chunk = rows_per_chunk(g);
@@ -998,6 +1056,7 @@ class HipBackend final : public Backend {
   }
   void init_random(void* buf, const TileGeom& g, uint64_t seed, double density, int64_t grow0,
                    int64_t gcol0) override {
+    quiet_.prev.T = 0;
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_init_random(static_cast<uint8_t*>(buf), g, seed, density_thresh(density), grow0, gcol0,
@@ -1077,8 +1136,12 @@ class HipBackend final : public Backend {
   hipk::LifeTuning tune_;
   hipStream_t comm_ = nullptr;
   // chain_mem: chained groups' flags, slots; linked launches' 3 x completion words.
-  void* chain_[5] = {};
-  size_t chain_bytes_[5] = {};
+  // 5, 6: the skipping kernel's tile-word maps; 7: its counters.
+  void* chain_[8] = {};
+  size_t chain_bytes_[8] = {};
+  hipk::QuietState quiet_;  // quiet-tile skipping (BlockArgs::quiet)
+  QuietTuning quiet_tune_;
+  int64_t quiet_tiles_ = 0;  // tiles launched by the skipping kernel
   hipk::LinkState link_;  // linked launches (GOL_LINK)
   bool link_on_ = false;  // every eligible launch (GOL_LINK=1)
   int link_mode_ = -1;

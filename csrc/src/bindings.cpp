@@ -315,6 +315,12 @@ PYBIND11_MODULE(_gol, m) {
       .def_property_readonly("poll_trial_ms_side", &Engine::poll_trial_ms_side)
       .def_property_readonly("poll_trial_ms_side_steady", &Engine::poll_trial_ms_side_steady)
       .def("triggered_sends", &Engine::triggered_sends)
+      .def("quiet_mode", &Engine::quiet_mode)
+      .def_property_readonly("quiet_blocks_dense", &Engine::quiet_blocks_dense)
+      .def_property_readonly("quiet_blocks_scout", &Engine::quiet_blocks_scout)
+      .def_property_readonly("quiet_blocks_skip", &Engine::quiet_blocks_skip)
+      .def_property_readonly("quiet_waves_launched", &Engine::quiet_waves_launched)
+      .def_property_readonly("quiet_waves_skipped", &Engine::quiet_waves_skipped)
       .def_property("phase_timing", &Engine::phase_timing, &Engine::set_phase_timing)
       .def("graphs", &Engine::graphs)
       .def_property("generation", &Engine::generation, &Engine::set_generation)
@@ -381,6 +387,45 @@ PYBIND11_MODULE(_gol, m) {
         if (create) create_text_file(path, e.decomp().W, e.decomp().H);
         write_text_tile(path, e.decomp().W, e.decomp().H, e.rows(), e.cols(), tile.data(), e.cols().size());
       }, py::arg("path"), py::arg("create") = true);
+
+  // ---- quiet-tile skipping: the pure decision logic (gol/quiet.hpp) ----
+  m.attr("QUIET_DIRTY") = quiet::kDirty;
+  m.attr("QUIET_TOP") = quiet::kTop;
+  m.attr("QUIET_BOT") = quiet::kBot;
+  m.attr("QUIET_LEFT") = quiet::kLeft;
+  m.attr("QUIET_RIGHT") = quiet::kRight;
+  m.def("quiet_may_skip", [](const std::vector<uint32_t>& nb) {
+    GOL_REQUIRE(nb.size() == 9, "quiet_may_skip: nine tile words (3 x 3, row-major)");
+    return quiet::may_skip(nb.data());
+  });
+  py::class_<quiet::Launch>(m, "QuietLaunch")
+      .def(py::init([](std::uintptr_t in, std::uintptr_t out, int T, int64_t row_lo, int64_t row_hi, int64_t pitch,
+                       int ncolw, int nseg, int seg_rows, int seg_rem, int grp_q, int wrap_w) {
+             return quiet::Launch{reinterpret_cast<const void*>(in), reinterpret_cast<const void*>(out), T, row_lo,
+                                  row_hi, pitch, ncolw, nseg, seg_rows, seg_rem, grp_q, wrap_w};
+           }),
+           py::arg("inp"), py::arg("out"), py::arg("T") = 12, py::arg("row_lo") = 32, py::arg("row_hi") = 800,
+           py::arg("pitch") = 768, py::arg("ncolw") = 3, py::arg("nseg") = 8, py::arg("seg_rows") = 96,
+           py::arg("seg_rem") = 0, py::arg("grp_q") = 27, py::arg("wrap_w") = 160);
+  m.def("quiet_may_follow", &quiet::may_follow);
+  py::class_<quiet::Policy>(m, "QuietPolicy")
+      .def(py::init([](int mode, int scout, int on, int off) {
+             quiet::Policy p;
+             p.mode = mode;
+             p.scout = scout;
+             p.on = on;
+             p.off = off;
+             return p;
+           }),
+           py::arg("mode") = -1, py::arg("scout") = 128, py::arg("on") = 60, py::arg("off") = 35)
+      .def("next", &quiet::Policy::next)
+      .def("ran", &quiet::Policy::ran)
+      .def("report", &quiet::Policy::report)
+      .def("name", &quiet::Policy::name)
+      .def_readonly("skipping", &quiet::Policy::skipping)
+      .def_readonly("blocks_dense", &quiet::Policy::blocks_dense)
+      .def_readonly("blocks_scout", &quiet::Policy::blocks_scout)
+      .def_readonly("blocks_skip", &quiet::Policy::blocks_skip);
 
   // ---- I/O ----
   m.def("read_text_tile", [](const std::string& path, int64_t W, int64_t H, int64_t r0, int64_t r1,

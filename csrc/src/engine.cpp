@@ -215,6 +215,20 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
                        (tr_->size() > 1 || cfg_.self_exchange);
   poll_side_ = side_ok && sp > 0 && !auto_overlap_;
   poll_trial_ = side_ok && sp < 0;
+  // Quiet-tile skipping (gol/quiet.hpp): single-rank B3/S23 ring tiles in the
+  // bit layout whose columns wrap, where every block covers exactly the owned
+  // rows at the skipping kernel's block size (the tiles of a launch then form
+  // a torus that is the same from block to block).  Everything else keeps
+  // today's path.
+  const Backend::QuietTuning qt = be_->quiet_mode();
+  if (qt.mode != 0 && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
+      tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_ && tmax_ == be_->quiet_block() && D_ == tmax_) {
+    quiet_.mode = qt.mode;
+    quiet_.scout = qt.scout;
+    quiet_.on = qt.on;
+    quiet_.off = qt.off;
+    be_->quiet_prepare(via_bits_ ? gb_ : g_);
+  }
   gen_ = cfg_.start_gen;
 }
 
@@ -601,11 +615,42 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
     for (int i = 0; i < 4; ++i) a.trigger_rows[i] = trigger_rows[i];
   }
   a.ring = rows_ring_;
+  // Quiet-tile skipping: blocks of the skipping kernel's size over the owned
+  // rows run it when the policy says so (on the DPP window: no drift, and the
+  // drift accumulated so far stays where it is).  Any other block leaves the
+  // next skipping block nothing to skip on (the backend sees to that).
+  const bool quiet_size = quiet_.mode != 0 && !capturing_ && !trigger_rows && T == be_->quiet_block() &&
+                          row_lo == g.Dv && row_hi == g.Dv + g.H;
+  if (quiet_size) {
+    quiet_poll();
+    a.quiet = quiet_.next();
+    if (a.quiet) {
+      a.allow_drift = false;
+      a.link = false;
+    }
+    quiet_.ran(a.quiet);
+  }
   void* t = phase_begin(nullptr);
   const int drift = be_->run_block(a);
   phase_end(kCompute, t, nullptr);
   ++launches_;
   return drift;
+}
+
+// The newest report of the skipping kernel the device has published (host-
+// mapped words: no synchronisation): feeds the policy, once per launch.
+void Engine::quiet_poll() {
+  int64_t seq = 0, tiles = 0, clean = 0, skipped = 0;
+  if (!be_->quiet_report(&seq, &tiles, &clean, &skipped)) return;
+  quiet_skipped_tiles_ = skipped;
+  if (seq == quiet_seq_seen_) return;
+  quiet_seq_seen_ = seq;
+  quiet_.report(tiles, clean);
+}
+
+int64_t Engine::quiet_waves_skipped() {
+  quiet_poll();
+  return quiet_skipped_tiles_ * be_->quiet_tile_waves();
 }
 
 void Engine::step_block(int T, int64_t row_lo, int64_t row_hi) {

@@ -32,6 +32,15 @@ const std::vector<TuningKey>& tuning_keys() {
       {"wrap", "GOL_WRAP", "1", 'i', "tune", "full-width tiles wrap column reads (no halo columns)"},
       {"fold", "GOL_FOLD", "1", 'i', "tune", "fold a narrow last column strip into the others' waves"},
       {"row_ring", "GOL_ROW_RING", "1", 'i', "tune", "single-rank tiles on a row ring (aliased halo rows)"},
+      {"quiet_skip", "GOL_QUIET_SKIP", "-1", 'i', "tune",
+       "skip temporal blocks over settled tiles (single-rank bit-layout ring tiles, T = 12): -1 auto (dense kernels "
+       "with a detecting scout block every quiet_scout blocks, the skipping kernel once quiet_on percent of the tiles "
+       "are clean, back below quiet_off), 0 off, 1 every block"},
+      {"quiet_scout", "GOL_QUIET_SCOUT", "128", 'i', "tune", "quiet_skip auto: blocks between two scout blocks"},
+      {"quiet_on", "GOL_QUIET_ON", "60", 'i', "tune", "quiet_skip auto: percent of clean tiles that starts skipping"},
+      {"quiet_off", "GOL_QUIET_OFF", "35", 'i', "tune", "quiet_skip auto: percent of clean tiles below which it stops"},
+      {"quiet_rows", "GOL_QUIET_ROWS", "96", 'i', "tune",
+       "output rows per 4-wave group (one tile) of the skipping kernel's plan"},
       {"u8_kernel", "GOL_U8_KERNEL", "auto", 's', "tune", "byte kernel on the bytes themselves: auto | lds"},
       {"lds_rows", "GOL_LDS_ROWS", "32", 'i', "tune", "rows per LDS tile of the byte LDS kernel"},
       {"lds_t", "GOL_LDS_T", "0", 'i', "tune", "generations per LDS pass (0: 32 packed, 8 unpacked)"},

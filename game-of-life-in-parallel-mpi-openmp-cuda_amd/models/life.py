@@ -258,6 +258,13 @@ class Simulation:
                 "u8_compute": ("bits" if self._eng.via_bits else "bytes") if self.config.resolved_layout() == "u8" else None,
                 "row_ring": bool(self._eng.row_ring), "row_ring_fallback": self._eng.row_ring_fallback or None,
                 "kernel": self._kernel_name(),
+                # Quiet-tile skipping (tuning quiet_skip): the mode, T-generation blocks run by
+                # the dense kernels / as scouts / by the skipping kernel, and its waves.
+                "quiet_mode": self._eng.quiet_mode(),
+                "quiet_blocks": {"dense": self._eng.quiet_blocks_dense, "scout": self._eng.quiet_blocks_scout,
+                                 "skip": self._eng.quiet_blocks_skip},
+                "quiet_waves_launched": self._eng.quiet_waves_launched,
+                "quiet_waves_skipped": self._eng.quiet_waves_skipped,
                 "tuning": self.tuning(), "tuning_changed": self.tuning_changed()}
 
     def tuning(self) -> dict[str, str]:

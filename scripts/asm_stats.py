@@ -54,15 +54,34 @@ def mix(ops):
     return c
 
 
+def resources(text):
+    """Per kernel, from the code object's metadata: VGPRs (with AGPRs),
+    scratch and LDS bytes, and the waves per SIMD the registers allow (512
+    registers per lane and SIMD, allocated in eights, at most 8 waves)."""
+    out = {}
+    for m in re.finditer(r"^\s+- \.agpr_count:.*?^\s+\.wavefront_size:", text, re.M | re.S):
+        f = dict(re.findall(r"^\s+(?:- )?\.(\w+):\s+(\S+)", m.group(0), re.M))
+        if "name" not in f:
+            continue
+        regs = int(f.get("vgpr_count", 0))
+        out[f["name"]] = {"vgpr": regs, "scratch": int(f.get("private_segment_fixed_size", 0)),
+                          "lds": int(f.get("group_segment_fixed_size", 0)),
+                          "waves_per_simd": min(8, 512 // max(8, (regs + 7) // 8 * 8))}
+    return out
+
+
 def main():
     text = open(sys.argv[1]).read()
     pats = sys.argv[2:]
+    res = resources(text)
     for name, body in kernels(text):
         if pats and not any(p in name for p in pats):
             continue
         seq = instrs(body)
         ops = [x[1] for x in seq if x[0] == "op"]
         print(f"{name[:110]}\n  whole: {mix(ops)}")
+        if name in res:
+            print(f"  resources: {res[name]}")
         labels = {x[1]: i for i, x in enumerate(seq) if x[0] == "label"}
         for i, x in enumerate(seq):
             if x[0] != "op" or not x[1].startswith("s_cbranch") and not x[1].startswith("s_branch"):
