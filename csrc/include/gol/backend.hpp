@@ -8,6 +8,7 @@
 //                   (epochs, halos, lazy termination) be tested without a GPU.
 #pragma once
 
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -108,6 +109,10 @@ class Backend {
   // it before enqueueing transport operations on stream() itself.
   virtual void join_streams() {}
   virtual int64_t linked_launches() const { return 0; }
+  // Launch census: run_block launches so far by the kernel path they took
+  // (HIP backend: classic, grouped, chained, linked, skipping, lds_tiled);
+  // empty where the backend has one path only.
+  virtual std::map<std::string, int64_t> launch_paths() const { return {}; }
   // Makes this backend's device current for the calling thread (rank
   // threads of single-process multi-GPU runs call it first).
   virtual void bind_thread() {}

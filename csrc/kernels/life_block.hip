@@ -28,7 +28,7 @@ const char* xlane_name(int x) { return x == kXlaneAuto ? "auto(add|dpp)" : x == 
 
 namespace {
 
-using VariantFn = void (*)(const LifeBlockParams&, int64_t, int, const LifeTuning&, hipStream_t);
+using VariantFn = LaunchResult (*)(const LifeBlockParams&, int64_t, int, const LifeTuning&, const LaunchCtx&, hipStream_t);
 struct RuleKernels {
   const char* name;
   Rule rule;
@@ -73,7 +73,7 @@ int life_block_max_T(Layout layout, const LifeTuning& tune) {
   return 16;
 }
 
-int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t stream) {
+LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const LaunchCtx& ctx, hipStream_t stream) {
   const TileGeom& g = a.g;
   GOL_REQUIRE(a.row_lo - a.T >= 0 && a.row_hi + a.T <= g.R() && a.row_lo < a.row_hi,
               "life_block: row range outside the tile");
@@ -101,8 +101,8 @@ int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t st
   } else {
     p.changed = a.changed ? a.changed + (a.gen_base + 1 - a.flags_base) : nullptr;
   }
-  p.wg_trace = tune.wg_trace;
-  p.err = tune.err;
+  p.wg_trace = ctx.wg_trace;
+  p.err = ctx.mail->err;
   p.chain_spin_log2 = tune.chain_spin_log2;
   p.wrap_w = a.full_width && tune.wrap && g.W % 32 == 0 ? int(g.W / 32) : 0;
   p.fold = 1;
@@ -129,44 +129,43 @@ int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t st
     // Packed tiles need 32-cell aligned rows (pitch) and owned cells.
     const bool pack = a.T >= 8 && (tune.lds_pack || a.T > 8) && g.pitch % 32 == 0 && g.cell0() % 32 == 0;
     GOL_REQUIRE(a.T <= 8 || pack, "life_block: LDS-tiled byte passes deeper than 8 need the packed tile");
-    if (pack) return launch_life_lds_bits(a, tune.wrap, tune.lds_xcd, tune.lds_waves, tune.cus, stream);
-    if (a.T == 1)
+    LaunchResult res;
+    res.path = kPathLdsTiled;
+    if (pack)
+      res.drift = launch_life_lds_bits(a, tune.wrap, tune.lds_xcd, tune.lds_waves, tune.cus, stream);
+    else if (a.T == 1)
       launch_life_step_lds(a, tune.lds_rows, tune.wrap, stream);
     else
       launch_life_lds_multi(a, tune.wrap, stream);
-    return 0;
+    return res;
   }
   // The adder window drifts the storage frame by T cells (see kXlaneAdd); the
   // engine allows that only for whole-width tiles of 32-cell words, and the
   // left halo must hold the 2T cells its one-sided light cone consumes (wrap
   // mode reads the wrapped owned words instead).
   // Quiet-tile skipping (BlockArgs::quiet): the detecting / skipping kernel
-  // where the block can be planned for it; else the kernels below, and the
-  // next skipping launch finds no words to read.
-  if (tune.quiet) {
-    if (a.quiet && !rk && g.layout == Layout::Bits && launch_bits_w1_dpp_quiet(p, rows, a.T, tune, stream)) return 0;
-    tune.quiet->prev.T = 0;
+  // where the block can be planned for it; else the kernels below (any path
+  // but kPathSkipping leaves the next skipping launch no words to read).
+  if (ctx.quiet && a.quiet && !rk && g.layout == Layout::Bits) {
+    LaunchResult res;
+    res.path = kPathSkipping;
+    res.quiet_tiles = launch_bits_w1_dpp_quiet(p, rows, a.T, ctx, stream);
+    if (res.quiet_tiles > 0) return res;
   }
   if (x == kXlaneAuto) x = kXlaneAdd;  // the engine decided through allow_drift
   // The one-sided window also consumes 2T cells of its wave's single halo
   // word per pass, so passes deeper than 16 (the byte layout's T = 24 / 32)
   // run the DPP window.
   if (x == kXlaneAdd && !(a.allow_drift && a.T <= 16 && (p.wrap_w > 0 || 32 * g.hw >= 2 * a.T))) x = kXlaneDpp;
-  if (rk) {
-    // No byte-layout adder variant: that request runs the DPP window.
-    if (x == kXlaneAdd && g.layout == Layout::Bits) {
-      rk->bits_add(p, rows, a.T, tune, stream);
-      return a.T;
-    }
-    (g.layout == Layout::U8 ? rk->u8_dpp : rk->bits_dpp)(p, rows, a.T, tune, stream);
-    return 0;
-  }
-  if (x == kXlaneAdd) {
-    (g.layout == Layout::U8 ? launch_u8_w1_add : launch_bits_w1_add)(p, rows, a.T, tune, stream);
-    return a.T;
-  }
-  (g.layout == Layout::U8 ? launch_u8_w1_dpp : launch_bits_w1_dpp)(p, rows, a.T, tune, stream);
-  return 0;
+  const bool u8 = g.layout == Layout::U8;
+  // No byte-layout adder variant of a rule: that request runs the DPP window.
+  if (rk && u8) x = kXlaneDpp;
+  const VariantFn fn = rk ? (x == kXlaneAdd ? rk->bits_add : u8 ? rk->u8_dpp : rk->bits_dpp)
+                          : x == kXlaneAdd ? (u8 ? launch_u8_w1_add : launch_bits_w1_add)
+                                           : (u8 ? launch_u8_w1_dpp : launch_bits_w1_dpp);
+  LaunchResult res = fn(p, rows, a.T, tune, ctx, stream);
+  res.drift = x == kXlaneAdd ? a.T : 0;
+  return res;
 }
 
 }  // namespace hipk

@@ -5,7 +5,7 @@
 namespace gol {
 namespace hipk {
 
-GOL_LIFE_VARIANT(launch_bits_w1_add) { lb::launch_variant<lb::BitsIO<1, kXlaneAdd>>(p, out_rows, T, tune, s); }
+GOL_LIFE_VARIANT(launch_bits_w1_add) { return lb::launch_variant<lb::BitsIO<1, kXlaneAdd>>(p, out_rows, T, tune, ctx, s); }
 
 }  // namespace hipk
 }  // namespace gol

@@ -4,7 +4,7 @@
 namespace gol {
 namespace hipk {
 
-GOL_LIFE_VARIANT(launch_bits_w1_dpp) { lb::launch_variant<lb::BitsIO<1, kXlaneDpp>>(p, out_rows, T, tune, s); }
+GOL_LIFE_VARIANT(launch_bits_w1_dpp) { return lb::launch_variant<lb::BitsIO<1, kXlaneDpp>>(p, out_rows, T, tune, ctx, s); }
 
 }  // namespace hipk
 }  // namespace gol

@@ -22,16 +22,18 @@ namespace lb {
 constexpr int kSplitMaxRowsPerT = 8;
 
 // Linked launch of the grouped kernel (LifeBlockParams::link_*): returns
-// false (nothing launched) when the launch cannot be planned that way.  The
-// first launch of a chain goes on stream[0] (the caller's `s`); a launch that
+// false (nothing launched) when the launch cannot be planned that way, else
+// fills *res (path, trigger_adds).  The first launch of a chain goes on
+// stream[0] (the caller's `s`); a launch that
 // reads the previous one's output and fits beside it goes on the other
 // stream, after an event recorded just before the previous launch (so it
 // starts no earlier than that one), and waits for its input rows group by
 // group.
 template <int T, class IO, int M = 8>
-bool launch_linked(const LifeBlockParams& p0, int64_t out_rows, int simds, const LifeTuning& tune, hipStream_t s) {
+bool launch_linked(const LifeBlockParams& p0, int64_t out_rows, int simds, const LifeTuning& tune,
+                   const LaunchCtx& ctx, hipStream_t s, LaunchResult* res) {
   using LIO = Sc1IO<IO>;
-  LinkState& L = *tune.link;
+  LinkState& L = *ctx.link;
   if (s != L.stream[0]) return false;
   LifeBlockParams q = p0;  // keeps launch_T's folded last strip (q.fold): a folded block publishes
                            // the completion words of all its groups
@@ -62,8 +64,7 @@ bool launch_linked(const LifeBlockParams& p0, int64_t out_rows, int simds, const
   // the previous launch, which may still run) are overwritten.
   const size_t need = size_t(q.ncolw) * size_t(q.nseg);  // one word per group
   if (L.flag_words < need) {
-    if (!tune.chain_mem) return false;
-    for (int i = 0; i < 3; ++i) L.flags[i] = tune.chain_mem(2 + i, need * 4);
+    for (int i = 0; i < 3; ++i) L.flags[i] = ctx.scratch->get(Scratch::kLinkWords[i], need * 4);
     L.flag_words = need;
     L.prev_valid = false;
     if (link) return false;  // the buffers moved under the previous launch: start a new chain
@@ -71,17 +72,15 @@ bool launch_linked(const LifeBlockParams& p0, int64_t out_rows, int simds, const
   if (++L.seq == 0) L.seq = 1;
   // Boundary trigger: count the groups meeting the trigger rows (the kernel
   // adds one per such group when it publishes).
-  L.bnd_n = 0;
   q.bnd_count = nullptr;
   for (int& g : q.bnd_g) g = 0;
-  if (L.bnd_req) {
-    const int n = trigger_groups(q, L.bnd_r, q.bnd_g);
-    if (L.bnd_count_req && L.bnd_count) {
-      L.bnd_n = int64_t(n) * q.ncolw;
-      q.bnd_count = L.bnd_count;
+  if (ctx.trigger.kind != TriggerReq::kNone) {
+    const int n = trigger_groups(q, ctx.trigger.rows, q.bnd_g);
+    if (ctx.trigger.kind == TriggerReq::kCounting && ctx.trigger.counter) {
+      res->trigger_adds = int64_t(n) * q.ncolw;
+      q.bnd_count = ctx.trigger.counter;
     }
   }
-  L.bnd_req = false;
   q.link_flag = L.flags[L.seq % 3];
   q.link_seq = L.seq;
   hipStream_t st = L.stream[0];
@@ -106,26 +105,24 @@ bool launch_linked(const LifeBlockParams& p0, int64_t out_rows, int simds, const
     // words (flags[seq % 3]) it overwrites.  After an armed boundary trigger
     // the stream's wait kernel already implies that start (LinkState::started).
     if (!L.started) (void)hipStreamWaitEvent(st, L.before[L.cur], 0);
-    ++L.linked;
   } else {
     link_join(L);
-    L.chain = 0;
   }
   (void)hipEventRecord(L.before[which], st);
-  ++L.chain;
   hipLaunchKernelGGL((life_group_kernel<T, LIO, M>), dim3(unsigned(blocks)), dim3(64 * M), 0, st, q);
+  res->path = link ? kPathLinked : kPathGrouped;
   L.started = false;
   L.cur = which;
   L.prev = q;
   L.prev_out = q.out;
-  L.prev_blocks = blocks;
   L.prev_share = share;
   L.prev_valid = true;
   return true;
 }
 
 template <int T, class IO>
-void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipStream_t s) {
+LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, const LaunchCtx& ctx, hipStream_t s) {
+  LaunchResult res;
   constexpr int kWaveOut = wave_out_words<IO::XL, IO::W>();
   // Wrap mode (p.wrap_w > 0) covers the owned words only (lane_cols).
   p.ncolw = int(ceil_div(p.wrap_w ? p.wrap_w : p.Wp, kWaveOut));
@@ -149,7 +146,7 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
   // still runs, on the other stream, when both fit on the GPU at once (small
   // tiles, whose launches alone hold 2 waves per SIMD).  Any other launch
   // first joins the two streams.
-  if (tune.link) {
+  if (ctx.link) {
     if constexpr (IO::Rule::kDefault && IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
                   (IO::XL == kXlaneDpp || IO::XL == kXlaneAdd)) {
       if (tune.group != 0) {
@@ -157,16 +154,16 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
         // group 4 waves (tune group_small).
         if constexpr (T <= 8) {
           if (tune.group_small == 4) {
-            if (launch_linked<T, IO, 4>(p, out_rows, simds, tune, s)) return;
-          } else if (launch_linked<T, IO>(p, out_rows, simds, tune, s)) {
-            return;
+            if (launch_linked<T, IO, 4>(p, out_rows, simds, tune, ctx, s, &res)) return res;
+          } else if (launch_linked<T, IO>(p, out_rows, simds, tune, ctx, s, &res)) {
+            return res;
           }
-        } else if (launch_linked<T, IO>(p, out_rows, simds, tune, s)) {
-          return;
+        } else if (launch_linked<T, IO>(p, out_rows, simds, tune, ctx, s, &res)) {
+          return res;
         }
       }
     }
-    link_join(*tune.link);
+    link_join(*ctx.link);
   }
   if constexpr (T >= 4) {
     // Bit-layout blocks of T <= 8 (small tiles, HipBackend::choose_kernel)
@@ -198,7 +195,7 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
       // strip's last.  Stream launches only (the flags count launches, so a
       // replayed graph would see its own stale flags).
       // Rule kernels (IO::Rule other than Conway) are never linked or chained.
-      if (IO::Rule::kDefault && tune.chain && tune.chain_ok && tune.chain_mem && tune.chain_seq) {
+      if (IO::Rule::kDefault && ctx.chain) {
         LifeBlockParams ch = p;
         ch.fold = 1;
         ch.fold_lanes = 64;
@@ -206,7 +203,7 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
         const double cch =
             m4 ? plan_chain<T, 4>(ch, out_rows, simds, group_waves_per_simd<T, IO, 4>(), tune.target_waves, IO::XL)
                : plan_chain<T, 8>(ch, out_rows, simds, group_waves_per_simd<T, IO, 8>(), tune.target_waves, IO::XL);
-        // tune.chain is set per launch by the backend (HipBackend's launch-
+        // ctx.chain is decided per launch by the backend (HipBackend's launch-
         // shape autotuning, or GOL_CHAIN=1 forced): +2 % on the 8-GPU rank
         // tile, -1 to -3 % on larger tiles and -12 % on 8192^2, where the
         // folded last strip it gives up is worth more; choosing it by the
@@ -214,36 +211,43 @@ void launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tune, hipSt
         if (cch > 0) {
           constexpr int64_t kSlot = int64_t(T - 1) * 2 * IO::W * 64;
           const int64_t slots = int64_t(ch.ncolw) * ch.nseg;
-          ch.chain_flag = tune.chain_mem(0, size_t(slots) * 4);
-          ch.chain_buf = tune.chain_mem(1, size_t(slots * kSlot) * 4);
-          if (++*tune.chain_seq == 0) *tune.chain_seq = 1;  // 0 = never written
-          ch.chain_seq = *tune.chain_seq;
-          return m4 ? launch_group<T, IO, 4>(ch, s) : launch_group<T, IO, 8>(ch, s);
+          ch.chain_flag = ctx.scratch->get(Scratch::kChainFlags, size_t(slots) * 4);
+          ch.chain_buf = ctx.scratch->get(Scratch::kChainSlots, size_t(slots * kSlot) * 4);
+          ch.chain_seq = ctx.scratch->next_chain_seq();
+          m4 ? launch_group<T, IO, 4>(ch, s) : launch_group<T, IO, 8>(ch, s);
+          res.path = kPathChained;
+          return res;
         }
       }
-      if (better(c4, c8) && better(c4, cc)) return launch_group<T, IO, 4>(g4, s);
-      if (better(c8, cc)) return launch_group<T, IO, 8>(g8, s);
+      const int m = better(c4, c8) && better(c4, cc) ? 4 : better(c8, cc) ? 8 : 0;
+      if (m) {
+        m == 4 ? launch_group<T, IO, 4>(g4, s) : launch_group<T, IO, 8>(g8, s);
+        res.path = kPathGrouped;
+        return res;
+      }
     }
   }
   plan(p, T, out_rows, simds, waves_per_simd<T, IO>(), tune.min_seg_rows, tune.target_waves, -1, nullptr, IO::XL);
   const int waves = p.ncolw * p.nseg;
   const dim3 grid(unsigned(ceil_div(waves, 4))), block(256);
   hipLaunchKernelGGL((life_block_kernel<T, IO>), grid, block, 0, s, p);
+  return res;
 }
 
 // Deep byte-layout passes (T = 24, 32): instantiated in translation units of
 // their own (life_block_u8_w1_*_t24 / _t32.hip, `extern template` in the
 // variant TU), so the build compiles them in parallel.
 template <int T, class IO>
-void launch_deep(const LifeBlockParams& p, int64_t out_rows, const LifeTuning& tune, hipStream_t s) {
-  launch_T<T, IO>(p, out_rows, tune, s);
+LaunchResult launch_deep(const LifeBlockParams& p, int64_t out_rows, const LifeTuning& tune, const LaunchCtx& ctx,
+                         hipStream_t s) {
+  return launch_T<T, IO>(p, out_rows, tune, ctx, s);
 }
 #define GOL_U8_DEEP(KW, T_, XL_)                                                                   \
   namespace gol {                                                                                  \
   namespace hipk {                                                                                 \
   namespace lb {                                                                                   \
-  KW template void launch_deep<T_, U8IO<1, XL_>>(const LifeBlockParams&, int64_t, const LifeTuning&, \
-                                                 hipStream_t);                                     \
+  KW template LaunchResult launch_deep<T_, U8IO<1, XL_>>(const LifeBlockParams&, int64_t, const LifeTuning&, \
+                                                         const LaunchCtx&, hipStream_t);           \
   }                                                                                                \
   }                                                                                                \
   }
@@ -251,27 +255,23 @@ void launch_deep(const LifeBlockParams& p, int64_t out_rows, const LifeTuning& t
 // Host entry point of one compiled variant (instantiated once per
 // translation unit, life_block_*.hip).
 template <class IO>
-void launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune, hipStream_t s) {
+LaunchResult launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune,
+                            const LaunchCtx& ctx, hipStream_t s) {
   switch (T) {
-    case 1: launch_T<1, IO>(p, out_rows, tune, s); break;
-    case 2: launch_T<2, IO>(p, out_rows, tune, s); break;
-    case 4: launch_T<4, IO>(p, out_rows, tune, s); break;
-    case 8: launch_T<8, IO>(p, out_rows, tune, s); break;
-    case 12: launch_T<12, IO>(p, out_rows, tune, s); break;
-    case 16: launch_T<16, IO>(p, out_rows, tune, s); break;
+    case 1: return launch_T<1, IO>(p, out_rows, tune, ctx, s);
+    case 2: return launch_T<2, IO>(p, out_rows, tune, ctx, s);
+    case 4: return launch_T<4, IO>(p, out_rows, tune, ctx, s);
+    case 8: return launch_T<8, IO>(p, out_rows, tune, ctx, s);
+    case 12: return launch_T<12, IO>(p, out_rows, tune, ctx, s);
+    case 16: return launch_T<16, IO>(p, out_rows, tune, ctx, s);
     case 24:  // byte layout only: fewer byte-grid passes per generation
       // (the adder window never runs T > 16: launch_life_block switches it to DPP)
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault) {
-        launch_deep<24, IO>(p, out_rows, tune, s);
-        break;
-      }
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault)
+        return launch_deep<24, IO>(p, out_rows, tune, ctx, s);
       [[fallthrough]];
     case 32:
       if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault) {
-        if (T == 32) {
-          launch_deep<32, IO>(p, out_rows, tune, s);
-          break;
-        }
+        if (T == 32) return launch_deep<32, IO>(p, out_rows, tune, ctx, s);
       }
       [[fallthrough]];
     default: fail("life_block: unsupported temporal block size " + std::to_string(T));
@@ -302,7 +302,7 @@ namespace rules {
   namespace hipk {                                                                             \
   GOL_LIFE_VARIANT(launch_rule_##name##_##variant) {                                           \
     using R = lb::LifeLike<lb::rules::kB_##name, lb::rules::kS_##name>;                        \
-    lb::launch_variant<IO_(XL_, R)>(p, out_rows, T, tune, s);                                  \
+    return lb::launch_variant<IO_(XL_, R)>(p, out_rows, T, tune, ctx, s);                      \
   }                                                                                            \
   }                                                                                            \
   }

@@ -6,7 +6,7 @@
 namespace gol {
 namespace hipk {
 
-GOL_LIFE_VARIANT(launch_u8_w1_add) { lb::launch_variant<lb::U8IO<1, kXlaneAdd>>(p, out_rows, T, tune, s); }
+GOL_LIFE_VARIANT(launch_u8_w1_add) { return lb::launch_variant<lb::U8IO<1, kXlaneAdd>>(p, out_rows, T, tune, ctx, s); }
 
 }  // namespace hipk
 }  // namespace gol

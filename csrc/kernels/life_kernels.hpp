@@ -3,7 +3,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -36,7 +35,7 @@ struct LifeBlockParams {
   // writes {block<<8 | wave, XCC_ID<<32 | HW_ID, start, end} (s_memrealtime,
   // 100 MHz) at wg_trace[4 * (block * M + wave)], below kWgTraceWaves waves.
   uint64_t* wg_trace;
-  // Device-visible error word (host-mapped, Backend::check_device_errors):
+  // Device-visible error word (Mailbox::err, Backend::check_device_errors):
   // a kernel that has to give up (life_short_kernel's bounded LDS hand-off
   // wait) sets it instead of continuing silently with invalid rows.
   uint32_t* err;
@@ -49,7 +48,7 @@ struct LifeBlockParams {
   // block in sub-strips of fold_lanes lanes; 1 = no folding.
   int fold;
   int fold_lanes;
-  // Chained groups (life_group_kernel, LifeTuning::chain; null chain_buf =
+  // Chained groups (life_group_kernel, LaunchCtx::chain; null chain_buf =
   // off): the last wave of group g ends like an inner wave, with the inverted
   // triangle fed by group g + 1's wave 0 through global memory, so no group
   // boundary keeps a redundant triangle.  Per (strip, group) slot: wave 0's
@@ -60,7 +59,7 @@ struct LifeBlockParams {
   uint32_t* chain_flag;
   uint32_t chain_seq;
   int64_t chain_end;
-  // Linked launches (LifeTuning::link, life_group_kernel<..., LINK = true>):
+  // Linked launches (LaunchCtx::link, life_group_kernel<..., LINK = true>):
   // this launch may run while the previous grouped launch, whose output is
   // its input, still runs.  Group (kcol, grp) first waits until every group
   // of that launch whose output rows it reads (its strip and the two beside
@@ -133,27 +132,25 @@ struct LinkState {
   int cur = 0;                                  // stream of the last launch
   bool prev_valid = false;                      // the last launch may be linked to
   const void* prev_out = nullptr;               // its output buffer
-  int64_t prev_blocks = 0;                      // its workgroups
   double prev_share = 0.0;                      // its workgroups / how many of them fit on the CUs
   LifeBlockParams prev{};                       // its plan and completion words
   uint32_t* flags[3] = {nullptr, nullptr, nullptr};  // completion words, rotating per launch
   size_t flag_words = 0;
   uint32_t seq = 0;
-  int64_t linked = 0;                           // launches that ran linked (diagnostics)
-  int chain = 0;  // launches in the current chain
   // The stream of the next launch already follows the last launch's start
   // (Backend::trigger_stream: its wait kernel returns only once that
   // launch's boundary groups are done), so a linked next launch needs no
   // cross-stream event wait (~10 us of device time on the epoch boundary).
   bool started = false;
-  // Boundary trigger of the next launch (BlockArgs::trigger): requested
-  // rows, the counter, and how many increments the launch will make
-  // (launch_linked sets it; 0: the launch could not carry the trigger).
-  bool bnd_req = false;
-  bool bnd_count_req = false;  // count (the trigger launch) or priority only (BlockArgs::hot)
-  int64_t bnd_r[4] = {0, 0, 0, 0};
-  unsigned long long* bnd_count = nullptr;
-  int64_t bnd_n = 0;
+};
+
+// Boundary trigger of one launch (BlockArgs::trigger / hot; linked launches
+// only): the groups meeting `rows` run at top issue priority, and in a
+// counting launch each adds one to *counter once its rows are written.
+struct TriggerReq {
+  enum Kind { kNone, kHot, kCounting } kind = kNone;
+  int64_t rows[4] = {0, 0, 0, 0};
+  unsigned long long* counter = nullptr;
 };
 
 // The groups of a grouped plan whose output rows meet the trigger rows
@@ -199,14 +196,49 @@ struct QuietState {
   int cur = 0;                     // map the last launch wrote
   uint32_t seq = 0;                // launches so far (24 bits reach the report)
   int64_t tiles = 0;               // tiles of the last launch
-  unsigned long long* report = nullptr;       // host-mapped report word (device alias)
-  const unsigned long long* report_host = nullptr;
   int seg_rows = 96;               // output rows per group the plan aims at (tuning quiet_rows)
 };
 
+// Words the kernels write for the host: one fine-grained pinned host
+// allocation, written through its device alias and read without a copy.
+struct Mailbox {
+  uint32_t err[4];  // LifeBlockParams::err: the code (check_device_errors), then a give-up's diagnostics
+  unsigned long long quiet_report[2];  // LifeBlockParams::quiet_report
+};
+
+// Device memory that persists across launches, owned by the backend: one
+// buffer per slot, grown on demand.  A grown buffer is new memory, zeroed
+// where the slot says so (flags and words compared with sequence numbers) by
+// a fill on the compute stream, which orders it before the launch it is for.
+class Scratch {
+ public:
+  enum Slot { kChainFlags, kChainSlots, kLinkWordsA, kLinkWordsB, kLinkWordsC, kQuietMapA, kQuietMapB, kQuietCounters, kSlots };
+  static constexpr Slot kLinkWords[3] = {kLinkWordsA, kLinkWordsB, kLinkWordsC};  // LinkState::flags
+  // The two compute streams (the second may be null), which both drain before
+  // a buffer is replaced; check_dev >= 0: every buffer handed out is checked
+  // to live on that device (tuning check_device).
+  void init(hipStream_t compute, hipStream_t linked, int check_dev) {
+    streams_[0] = compute, streams_[1] = linked, check_dev_ = check_dev;
+  }
+  uint32_t* get(Slot slot, size_t bytes);  // at least `bytes` bytes of the slot's buffer
+  // The chain flags' launch counter (0 = never written).
+  uint32_t next_chain_seq() {
+    if (++chain_seq_ == 0) chain_seq_ = 1;
+    return chain_seq_;
+  }
+  void release();
+
+ private:
+  hipStream_t streams_[2] = {nullptr, nullptr};
+  int check_dev_ = -1;
+  void* buf_[kSlots] = {};
+  size_t bytes_[kSlots] = {};
+  uint32_t chain_seq_ = 0;
+};
+
+// Construction-time knobs of the launchers (Tuning, read once by HipBackend).
 struct LifeTuning {
   int cus = 256;            // compute units of the device
-  QuietState* quiet = nullptr;  // quiet-tile skipping state (launch_bits_w1_dpp_quiet)
   int target_waves = 0;     // waves per launch round (0 = occupancy x CUs x 4 SIMDs)
   int min_seg_rows = 16;    // lower bound on rows per wave segment
   int xlane = kXlaneAuto;   // cross-lane primitive
@@ -220,23 +252,35 @@ struct LifeTuning {
   int group_small = 4;      // the same for bit-layout blocks of T <= 8 (GOL_GROUP_SMALL; GOL_GROUP sets both)
   bool wrap = true;         // wrap mode on whole-width tiles (BlockArgs::full_width, lane_cols)
   bool fold = true;         // folded last strip in wrap mode (life_group_kernel)
-  int chain = 0;            // chained groups (LifeBlockParams::chain_buf): 0 off, 1 on, 2 timing probe
-  bool chain_ok = false;    // this launch may use the chain memory (the backend's own stream, not captured)
-  uint32_t* chain_seq = nullptr;  // host launch counter of the chain flags
-  // Device memory of at least n bytes that persists across launches, stream-
-  // ordered like `scratch`: which = 0 the chain flags (zeroed when allocated),
-  // 1 the chain slots.
-  std::function<uint32_t*(int which, size_t n)> chain_mem;
-  LinkState* link = nullptr;     // linked launches on (null: every launch on the given stream)
-  uint64_t* wg_trace = nullptr;  // per-wave placement/timing record of the next launch (LifeBlockParams)
-  uint32_t* err = nullptr;       // LifeBlockParams::err (4 words: code, then a give-up's diagnostics)
-  int chain_spin_log2 = 16;      // LifeBlockParams::chain_spin_log2
+  int chain = 0;            // chained groups (GOL_CHAIN): 0 off, 1 on, -1 autotuned per launch shape
+  int chain_spin_log2 = 16;  // LifeBlockParams::chain_spin_log2
   int fault_delay = 0;  // LifeBlockParams::fault_delay (GOL_FAULT_DELAY_SPINS)
 };
 
-// Returns the storage-frame drift of the launch in cells (T for the adder
-// window, 0 otherwise; BlockArgs::allow_drift).
-int launch_life_block(const BlockArgs& a, const LifeTuning& tune, hipStream_t stream);
+// What one launch_life_block call may use and was asked for, built by the
+// backend for that launch alone.
+struct LaunchCtx {
+  Scratch* scratch = nullptr;    // the backend's, always set
+  Mailbox* mail = nullptr;       // its device alias, always set
+  LinkState* link = nullptr;     // the launch may join a linked chain (null: it runs on the given stream)
+  QuietState* quiet = nullptr;   // the launch may run the skipping kernel
+  bool chain = false;            // chained groups (LifeBlockParams::chain_buf) where the plan allows
+  uint64_t* wg_trace = nullptr;  // per-wave placement/timing record (LifeBlockParams::wg_trace)
+  TriggerReq trigger;
+};
+
+// Which kernel a launch ran (the backend's launch census, Backend::launch_paths).
+enum LaunchPath : int { kPathClassic, kPathGrouped, kPathChained, kPathLinked, kPathSkipping, kPathLdsTiled, kLaunchPaths };
+constexpr const char* kLaunchPathNames[kLaunchPaths] = {"classic", "grouped", "chained", "linked", "skipping", "lds_tiled"};
+
+struct LaunchResult {
+  LaunchPath path = kPathClassic;  // kPathLinked: a launch that overlaps the previous one
+  int drift = 0;  // storage-frame drift in cells (T for the adder window, else 0; BlockArgs::allow_drift)
+  int64_t trigger_adds = 0;  // increments a counting launch makes to TriggerReq::counter (0: it carries none)
+  int64_t quiet_tiles = 0;   // tiles of a skipping launch
+};
+
+LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const LaunchCtx& ctx, hipStream_t stream);
 // The Life-like rules compiled for the HIP engine besides B3/S23
 // (life_rules.def), and whether launch_life_block runs `r`.
 std::vector<Rule> life_block_rules();
@@ -249,17 +293,17 @@ int life_block_max_T(Layout layout, const LifeTuning& tune);
 // Compiled variants (one translation unit each): the DPP and adder windows,
 // bit and byte layouts, one 32-cell word per lane.
 #define GOL_LIFE_VARIANT(name) \
-  void name(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune, hipStream_t s)
+  LaunchResult name(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune, const LaunchCtx& ctx, hipStream_t s)
 GOL_LIFE_VARIANT(launch_bits_w1_dpp);
 GOL_LIFE_VARIANT(launch_u8_w1_dpp);
 GOL_LIFE_VARIANT(launch_bits_w1_add);
 GOL_LIFE_VARIANT(launch_u8_w1_add);
 // The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave
 // groups of short segments; life_block_bits_w1_dpp_quiet.hip): wrap-mode
-// blocks over a row ring's owned rows only.  Returns false (nothing
-// launched) where the block cannot be planned that way.
-bool launch_bits_w1_dpp_quiet(const LifeBlockParams& p, int64_t out_rows, int T, const LifeTuning& tune, hipStream_t s);
-void prepare_bits_w1_dpp_quiet(const LifeTuning& tune, int64_t H, int64_t words);
+// blocks over a row ring's owned rows only.  Returns the tiles launched, 0
+// (nothing launched) where the block cannot be planned that way.
+int64_t launch_bits_w1_dpp_quiet(const LifeBlockParams& p, int64_t out_rows, int T, const LaunchCtx& ctx, hipStream_t s);
+void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words);
 constexpr int kQuietT = 12;
 // LifeBlockParams::quiet_count, in 64-bit words a cache line apart: the
 // launch's counter, the tiles skipped by all launches, kQuietCounters

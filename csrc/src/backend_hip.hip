@@ -38,6 +38,14 @@ namespace {
   DeviceScope device_scope_(dev_);   \
   if (check_dev_) assert_current(__func__)
 
+void check_on_device(int dev, const void* p, const char* what) {
+  if (!p) return;
+  hipPointerAttribute_t at{};
+  HIP_CHECK(hipPointerGetAttributes(&at, p));
+  GOL_REQUIRE(at.device == dev, std::string("GOL_CHECK_DEVICE: ") + what + " lives on device " +
+                                    std::to_string(at.device) + ", backend owns device " + std::to_string(dev));
+}
+
 class HipBackend final : public Backend {
  public:
   HipBackend(int device, const Tuning& t) : Backend(t), dev_(device) {
@@ -95,8 +103,8 @@ class HipBackend final : public Backend {
     tune_.group_small = !t.is_default("group") && t.is_default("group_small") ? tune_.group : t.i("group_small");
     tune_.wrap = t.on("wrap");
     tune_.fold = t.on("fold");
-    chain_mode_ = t.i("chain");
-    GOL_REQUIRE(chain_mode_ >= -1 && chain_mode_ <= 1, "tuning chain: -1, 0 or 1");
+    tune_.chain = t.i("chain");
+    GOL_REQUIRE(tune_.chain >= -1 && tune_.chain <= 1, "tuning chain: -1, 0 or 1");
     // Linked launches: consecutive grouped launches of an epoch overlap on
     // two streams, ordered by per-group completion words (LifeBlockParams::
     // link_*): small tiles whose launches alone hold only 2 waves per SIMD.
@@ -121,34 +129,14 @@ class HipBackend final : public Backend {
     // bounded cross-workgroup wait: no chained groups or linked launches there
     // (a rank tile's launch does not fit its slice twice anyway).
     if (!cu_part_.empty()) {
-      chain_mode_ = 0;
+      tune_.chain = 0;
       link_mode_ = 0;
       link_on_ = false;
     }
-    tune_.chain = chain_mode_ < 0 ? 0 : chain_mode_;
     tune_.fault_delay = std::max(0, std::min(4096, t.i("fault_delay_spins")));
     tune_log_ = t.on("tune_log");
     trigger_ok_ = link_mode_ != 0;  // armed only on linked launches
-    tune_.chain_seq = &chain_seq_;
-    // which: 0 chain flags, 1 chain slots, 2..4 linked-launch completion words
-    // (zeroed when allocated: flags and words are compared with sequence
-    // numbers).
-    tune_.chain_mem = [this](int which, size_t n) -> uint32_t* {
-      void*& buf = chain_[which];
-      size_t& cap = chain_bytes_[which];
-      if (n > cap) {
-        GOL_ON_DEVICE();
-        HIP_CHECK(hipStreamSynchronize(stream_));  // earlier launches may still use it
-        if (link_.stream[1]) HIP_CHECK(hipStreamSynchronize(link_.stream[1]));
-        if (buf) HIP_CHECK(hipFree(buf));
-        HIP_CHECK(hipMalloc(&buf, n));
-        if (which != 1) HIP_CHECK(hipMemsetAsync(buf, 0, n, stream_));  // ordered before the launch on stream_
-        cap = n;
-      }
-      if (check_dev_)
-        check_ptr(buf, which == 0 ? "chain flags" : which == 1 ? "chain slots" : which < 5 ? "link words" : "quiet words");
-      return static_cast<uint32_t*>(buf);
-    };
+    scratch_.init(stream_, link_.stream[1], check_dev_ ? dev_ : -1);
     if (split_trace(t.s("wg_trace"), &trace_at_, &trace_path_)) {
       // "N:path:pair": launches N and N + 1, left linked (overlap evidence).
       const size_t c2 = trace_path_.rfind(":pair");
@@ -157,21 +145,19 @@ class HipBackend final : public Backend {
         trace_path_ = trace_path_.substr(0, c2);
       }
     }
-    // Kernel error word: fine-grained pinned host memory the kernels write
-    // through its device alias and the host reads without a copy.
-    // Words 4..7: the skipping kernel's two 64-bit report words (QuietState).
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_host_), 8 * sizeof(uint32_t), hipHostMallocMapped));
-    for (int i = 0; i < 8; ++i) err_host_[i] = 0;
+    // The kernels' mailbox (error and report words): fine-grained pinned host
+    // memory they write through its device alias and the host reads without
+    // a copy.
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&mail_host_), sizeof(hipk::Mailbox), hipHostMallocMapped));
+    *mail_host_ = hipk::Mailbox{};
     tune_.chain_spin_log2 = std::min(24, std::max(4, t.i("chain_spin")));
-    HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&tune_.err), err_host_, 0));
+    HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&mail_dev_), mail_host_, 0));
     // Quiet-tile skipping (tuning quiet_skip; gol/quiet.hpp).
     quiet_tune_.mode = std::max(-1, std::min(1, t.i("quiet_skip")));
     quiet_tune_.scout = std::max(1, t.i("quiet_scout"));
     quiet_tune_.on = t.i("quiet_on");
     quiet_tune_.off = std::min(t.i("quiet_off"), quiet_tune_.on);
     quiet_.seg_rows = std::max(1, t.i("quiet_rows"));
-    quiet_.report = reinterpret_cast<unsigned long long*>(tune_.err + 4);
-    quiet_.report_host = reinterpret_cast<const unsigned long long*>(err_host_ + 4);
     if (!cu_part_.empty()) quiet_tune_.mode = 0;
   }
   static std::atomic<int>& live_backends(int dev) {
@@ -193,15 +179,16 @@ class HipBackend final : public Backend {
     for (auto& kv : rings_) release_ring(kv.second);
     if (stage_) hipFree(stage_);
     if (trigger_mem_) hipFree(trigger_mem_);
-    for (void* c : chain_)
-      if (c) hipFree(c);
+    scratch_.release();
+    for (uint64_t* d : trace_buf_)
+      if (d) hipFree(d);
     for (auto& p : pending_) {
       hipEventDestroy(p.e0);
       hipEventDestroy(p.e1);
     }
     for (hipEvent_t e : free_events_) hipEventDestroy(e);
     for (hipEvent_t e : timing_pool_) hipEventDestroy(e);
-    if (err_host_) hipHostFree(err_host_);
+    if (mail_host_) hipHostFree(mail_host_);
     for (auto& e : tail_)
       if (e) hipEventDestroy(e);
     if (comm_) hipStreamDestroy(comm_);
@@ -220,21 +207,21 @@ class HipBackend final : public Backend {
       hipk::link_join(link_);
     }
   }
-  int64_t linked_launches() const override { return link_.linked; }
+  int64_t linked_launches() const override { return census_.launches[hipk::kPathLinked]; }
   QuietTuning quiet_mode() const override { return quiet_tune_; }
   int quiet_block() const override { return hipk::kQuietT; }
   void quiet_invalidate() override { quiet_.prev.T = 0; }
   void quiet_prepare(const TileGeom& g) override {
     if (quiet_tune_.mode == 0 || g.layout != Layout::Bits) return;
     GOL_ON_DEVICE();
-    hipk::prepare_bits_w1_dpp_quiet(tune_, g.H, g.W / 32);
+    hipk::prepare_bits_w1_dpp_quiet(scratch_, g.H, g.W / 32);
   }
   bool quiet_report(int64_t* seq, int64_t* tiles, int64_t* clean, int64_t* skipped_total) override {
     if (quiet_.seq == 0) return false;
     // Two aligned 64-bit words the device stores whole; the newest launch's
     // words may still be on their way (the policy may lag).
-    const unsigned long long all = __atomic_load_n(quiet_.report_host + 1, __ATOMIC_ACQUIRE);
-    const unsigned long long r = __atomic_load_n(quiet_.report_host, __ATOMIC_ACQUIRE);
+    const unsigned long long all = __atomic_load_n(&mail_host_->quiet_report[1], __ATOMIC_ACQUIRE);
+    const unsigned long long r = __atomic_load_n(&mail_host_->quiet_report[0], __ATOMIC_ACQUIRE);
     if (r == 0) return false;
     // The report carries 24 bits of the launch number: the newest launch at
     // or before the last one issued with those bits.
@@ -247,13 +234,16 @@ class HipBackend final : public Backend {
     return true;
   }
   int quiet_tile_waves() const override { return 4; }
-  int64_t quiet_tiles_launched() const override { return quiet_tiles_; }
+  int64_t quiet_tiles_launched() const override { return census_.quiet_tiles; }
+  std::map<std::string, int64_t> launch_paths() const override {
+    std::map<std::string, int64_t> m;
+    for (int i = 0; i < hipk::kLaunchPaths; ++i) m[hipk::kLaunchPathNames[i]] = census_.launches[i];
+    return m;
+  }
   std::string name() const override {
-    hipk::LifeTuning t = tune_;
-    t.chain = chain_mode_;
     const std::string numa = numa_ >= 0 ? " numa=" + std::to_string(numa_) + ":" + std::to_string(numa_cpus_) + "cpus" : "";
-    return "hip:" + std::to_string(dev_) + ":" + arch_ + cu_part_ + numa + " [" + hipk::life_block_variant(Layout::Bits, t) +
-           "; " + hipk::life_block_variant(Layout::U8, t) + "]";
+    return "hip:" + std::to_string(dev_) + ":" + arch_ + cu_part_ + numa + " [" +
+           hipk::life_block_variant(Layout::Bits, tune_) + "; " + hipk::life_block_variant(Layout::U8, tune_) + "]";
   }
   int preferred_tmax(Layout l) const override { return hipk::life_block_max_T(l, tune_); }
   bool is_device() const override { return true; }
@@ -603,7 +593,7 @@ class HipBackend final : public Backend {
     *armed = false;
     if (trigger_target_ && link_.stream[1] && link_.cur == 1 && link_.prev_valid) {
       GOL_ON_DEVICE();
-      hipk::launch_wait_counter(trigger_counter(), trigger_target_, tune_.err, stream_);
+      hipk::launch_wait_counter(trigger_counter(), trigger_target_, mail_dev_->err, stream_);
       HIP_CHECK(hipGetLastError());
       link_.started = true;  // the next launch on this stream follows the trigger launch's start
       *armed = true;
@@ -634,64 +624,71 @@ class HipBackend final : public Backend {
       check_ptr(a.out, "run_block output");
     }
     const bool capturing = capturing_;  // capture_begin / capture_end (no query per launch)
-    // A launch may join a linked chain only outside a capture, for the bit
-    // layout; anything else first joins.
     // Rule kernels (any rule but B3/S23) are never linked or chained, forced
     // link=1 / chain=1 included.
     const bool conway = rule_is_default(a.rule);
+    // Wave trace: launch trace_at_ (its `pair` form: and the next one).
+    const int64_t traced = trace_at_ < 0 ? -1 : launches_ - trace_at_;
+    const bool trace = traced == 0 || (traced == 1 && trace_pair_);
     // Quiet-tile skipping: stream launches on the compute stream, never
-    // linked, chained or traced; any other block leaves the next skipping
-    // launch no words to read.
+    // linked, chained or traced.
     const bool quiet = a.quiet && quiet_tune_.mode != 0 && conway && !capturing && a.g.layout == Layout::Bits &&
                        trace_at_ < 0;
-    tune_.quiet = quiet ? &quiet_ : nullptr;
-    if (!quiet) quiet_.prev.T = 0;
+    // A launch may join a linked chain only outside a capture, for the bit
+    // layout (a single traced launch runs alone); anything else first joins.
     const bool linkable = !quiet && conway && (link_on_ || (a.link && link_mode_ < 0)) && link_.stream[1] &&
-                          !capturing && a.g.layout == Layout::Bits;
+                          !capturing && a.g.layout == Layout::Bits && !(trace && !trace_pair_);
     if (!linkable) join_streams();
-    tune_.link = linkable ? &link_ : nullptr;
-    if (chain_mode_) {  // chained groups: own stream only, never inside a graph capture
-      tune_.chain_ok = !capturing && !linkable;
-    }
-    if (trace_at_ >= 0 && trace_pair_ && (launches_ == trace_at_ || launches_ == trace_at_ + 1))
-      return run_block_traced_pair(a, linkable);
-    if (trace_at_ >= 0 && launches_ == trace_at_) {
-      join_streams();
-      tune_.link = nullptr;
-      return run_block_traced(a);
-    }
-    ++launches_;
-    hipStream_t s = stream_;
+    hipk::LaunchCtx ctx;
+    ctx.scratch = &scratch_;
+    ctx.mail = mail_dev_;
+    ctx.link = linkable ? &link_ : nullptr;
+    ctx.quiet = quiet ? &quiet_ : nullptr;
     // Boundary trigger: armed only if the launch runs linked (the grouped
     // kernel's publish path counts the boundary groups).
-    trigger_target_ = 0;
-    link_.bnd_n = 0;
-    link_.bnd_req = (a.trigger || a.hot) && linkable && trigger_counter();
-    link_.bnd_count_req = a.trigger;
-    if (link_.bnd_req) {
-      for (int i = 0; i < 4; ++i) link_.bnd_r[i] = a.trigger_rows[i];
-      link_.bnd_count = trigger_counter();
+    if ((a.trigger || a.hot) && linkable && trigger_counter()) {
+      ctx.trigger.kind = a.trigger ? hipk::TriggerReq::kCounting : hipk::TriggerReq::kHot;
+      std::copy(a.trigger_rows, a.trigger_rows + 4, ctx.trigger.rows);
+      ctx.trigger.counter = trigger_counter();
     }
-    Pending* timed = nullptr;
-    if (chain_mode_ < 0 && !linkable && conway && !quiet) timed = autotune_chain(a);
-    if (linkable) tune_.chain = 0;
-    const int64_t quiet_seq0 = quiet_.seq;
-    const int chain_kept = tune_.chain;
-    if (!conway) tune_.chain = 0;
-    if (timed) HIP_CHECK(hipEventRecord(timed->e0, s));
+    // Chained groups: the backend's own stream only (not linked), never
+    // inside a graph capture.
+    Pending trial{{}, -1, nullptr, nullptr};  // opt >= 0: a timed trial of that option (autotune_chain)
+    if (conway && !linkable && !capturing)
+      ctx.chain = tune_.chain > 0 || (tune_.chain < 0 && !quiet && autotune_chain(a, &trial));
+    if (trace) ctx.wg_trace = trace_begin(a, int(traced));
+    const hipStream_t s = stream_;
+    if (trial.opt >= 0) {  // its events leave the pool once the launch is in
+      while (free_events_.size() < 2) {
+        free_events_.emplace_back();
+        HIP_CHECK(hipEventCreate(&free_events_.back()));
+      }
+      trial.e0 = free_events_.end()[-1];
+      trial.e1 = free_events_.end()[-2];
+      HIP_CHECK(hipEventRecord(trial.e0, s));
+    }
     const auto l0 = prof_on_ ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
-    const int drift = hipk::launch_life_block(a, tune_, s);
+    const hipk::LaunchResult r = hipk::launch_life_block(a, tune_, ctx, s);
     if (prof_on_) prof_launch_ += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - l0).count();
-    tune_.chain = chain_kept;
     HIP_CHECK(hipGetLastError());
-    if (quiet_.seq != quiet_seq0) quiet_tiles_ += quiet_.tiles;
-    if (timed) HIP_CHECK(hipEventRecord(timed->e1, s));
-    if (a.trigger && link_.bnd_n > 0) {  // the linked kernel carries the counter
-      trigger_total_ += uint64_t(link_.bnd_n);
-      trigger_target_ = trigger_total_;
+    if (trial.opt >= 0) {
+      free_events_.resize(free_events_.size() - 2);
+      HIP_CHECK(hipEventRecord(trial.e1, s));
+      ++tuned_[trial.key].issued[trial.opt];
+      pending_.push_back(trial);
     }
-    link_.bnd_req = false;
-    return drift;
+    ++launches_;
+    ++census_.launches[r.path];
+    // Any launch but the skipping kernel's leaves the next skipping launch no
+    // words to read.
+    if (r.path == hipk::kPathSkipping)
+      census_.quiet_tiles += r.quiet_tiles;
+    else
+      quiet_invalidate();
+    // A counting launch arms the trigger (the linked kernel carries the counter).
+    trigger_target_ = r.trigger_adds > 0 ? (trigger_total_ += uint64_t(r.trigger_adds)) : 0;
+    if (trace) trace_end(a, int(traced), linkable);
+    return r.drift;
   }
 
   // Launch-shape autotuning of the chained groups (GOL_CHAIN=-1).  Chaining
@@ -715,24 +712,18 @@ class HipBackend final : public Backend {
     int opt;
     hipEvent_t e0, e1;
   };
-  Pending* autotune_chain(const BlockArgs& a) {
+  // Whether this launch chains; a timed trial launch gets its key and option.
+  bool autotune_chain(const BlockArgs& a, Pending* trial) {
     collect_tuning();
-    tune_.chain = 0;
-    if (!tune_.chain_ok) return nullptr;
     const TuneKey key{int64_t(a.g.layout), a.T, (a.row_hi - a.row_lo) >> 8, a.g.Wp(), a.allow_drift,
                       a.full_width};
-    TuneStats& st = tuned_[key];
-    if (st.pick >= 0) {
-      tune_.chain = st.pick;
-      return nullptr;
-    }
+    const TuneStats& st = tuned_[key];
+    if (st.pick >= 0) return st.pick != 0;
     const int opt = st.issued[0] <= st.issued[1] ? 0 : 1;
-    if (st.issued[opt] >= kTrials) return nullptr;  // trials in flight: plain kernel, untimed
-    ++st.issued[opt];
-    tune_.chain = opt;
-    Pending p{key, opt, event_take(), event_take()};
-    pending_.push_back(p);
-    return &pending_.back();
+    if (st.issued[opt] >= kTrials) return false;  // trials in flight: plain kernel, untimed
+    trial->key = key;
+    trial->opt = opt;
+    return opt != 0;
   }
   void collect_tuning() {
     while (!pending_.empty()) {
@@ -760,16 +751,6 @@ class HipBackend final : public Backend {
       free_events_.push_back(p.e1);
       pending_.pop_front();
     }
-  }
-  hipEvent_t event_take() {
-    if (free_events_.empty()) {
-      hipEvent_t e;
-      HIP_CHECK(hipEventCreate(&e));
-      return e;
-    }
-    hipEvent_t e = free_events_.back();
-    free_events_.pop_back();
-    return e;
   }
   bool drifts(Layout l) const override {
     if (l == Layout::U8 && tune_.u8_lds) return false;  // the LDS-tiled byte kernels run the DPP window
@@ -873,7 +854,7 @@ class HipBackend final : public Backend {
   // The LDS-tiled byte kernels read rows modulo the torus too.
   bool wraps_rows(Layout l) const override { return tune_.wrap && l == Layout::U8 && tune_.u8_lds; }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_rotate_cols(static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), g, shift, stream_);
@@ -881,7 +862,7 @@ class HipBackend final : public Backend {
   }
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t i0,
                     int64_t n) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_convert_rows(static_cast<const uint8_t*>(src), gs, static_cast<uint8_t*>(dst), gd, i0, n,
@@ -891,89 +872,55 @@ class HipBackend final : public Backend {
   // GOL_WG_TRACE=<launch index>:<csv path>: one life_block launch records
   // where and when each of its waves ran (grouped kernel, LifeBlockParams::
   // wg_trace); scripts/wg_trace.py turns the CSV into a per-CU makespan view.
-  int run_block_traced(const BlockArgs& a) {
-    ++launches_;
-    const size_t bytes = size_t(hipk::kWgTraceWaves) * 4 * sizeof(uint64_t);
-    uint64_t* d = nullptr;
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    HIP_CHECK(hipMalloc(&d, bytes));
-    HIP_CHECK(hipMemsetAsync(d, 0, bytes, stream_));
-    tune_.wg_trace = d;
-    const int drift = hipk::launch_life_block(a, tune_, stream_);
-    tune_.wg_trace = nullptr;
-    HIP_CHECK(hipGetLastError());
-    std::vector<uint64_t> h(size_t(hipk::kWgTraceWaves) * 4);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    HIP_CHECK(hipFree(d));
-    std::FILE* f = std::fopen(trace_path_.c_str(), "w");
-    GOL_REQUIRE(f != nullptr, "GOL_WG_TRACE: cannot open " + trace_path_);
-    std::fprintf(f, "block,wave,xcc_id,hw_id,t_start,t_end,T,rows\n");
-    for (int64_t i = 0; i < hipk::kWgTraceWaves; ++i) {
-      const uint64_t* r = &h[size_t(4 * i)];
-      if (!(r[0] >> 63)) continue;
-      std::fprintf(f, "%llu,%llu,%llu,%llu,%llu,%llu,%d,%lld\n", (unsigned long long)((r[0] & ~(1ull << 63)) >> 8),
-                   (unsigned long long)(r[0] & 255), (unsigned long long)(r[1] >> 32),
-                   (unsigned long long)(r[1] & 0xFFFFFFFFull), (unsigned long long)r[2], (unsigned long long)r[3],
-                   a.T, (long long)(a.row_hi - a.row_lo));
-    }
-    std::fclose(f);
-    return drift;
-  }
   // GOL_WG_TRACE=N:path:pair: per-wave records of launches N and N + 1 with
   // the second one left linked to the first (scripts/wg_trace.py --pair
-  // reports how far they overlapped).  Buffers are set up before launch N.
-  int run_block_traced_pair(const BlockArgs& a, bool linkable) {
-    const size_t bytes = size_t(hipk::kWgTraceWaves) * 4 * sizeof(uint64_t);
-    const int which = int(launches_ - trace_at_);
+  // reports how far they overlapped).  The buffers are set up before launch
+  // N, which starts a new linked chain, and written out after the last one.
+  uint64_t* trace_begin(const BlockArgs& a, int which) {
     if (which == 0) {
       join_streams();
       HIP_CHECK(hipStreamSynchronize(stream_));
-      for (auto& d : pair_trace_) {
-        HIP_CHECK(hipMalloc(&d, bytes));
-        HIP_CHECK(hipMemsetAsync(d, 0, bytes, stream_));
+      for (int l = 0; l <= int(trace_pair_); ++l) {
+        if (!trace_buf_[l]) HIP_CHECK(hipMalloc(&trace_buf_[l], kTraceBytes));
+        HIP_CHECK(hipMemsetAsync(trace_buf_[l], 0, kTraceBytes, stream_));
       }
       HIP_CHECK(hipStreamSynchronize(stream_));
-      pair_T_ = a.T;
+      trace_T_ = a.T;
     }
-    ++launches_;
-    hipStream_t s = stream_;
-    if (linkable) tune_.chain = 0;
-    tune_.wg_trace = pair_trace_[which];
-    const int drift = hipk::launch_life_block(a, tune_, s);
-    tune_.wg_trace = nullptr;
-    HIP_CHECK(hipGetLastError());
-    if (which == 1) {
-      join_streams();
-      HIP_CHECK(hipStreamSynchronize(stream_));
-      std::FILE* f = std::fopen(trace_path_.c_str(), "w");
-      GOL_REQUIRE(f != nullptr, "GOL_WG_TRACE: cannot open " + trace_path_);
-      std::fprintf(f, "launch,block,wave,xcc_id,hw_id,t_start,t_end,T,linked\n");
-      std::vector<uint64_t> h(size_t(hipk::kWgTraceWaves) * 4);
-      for (int l = 0; l < 2; ++l) {
-        HIP_CHECK(hipMemcpy(h.data(), pair_trace_[l], bytes, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < hipk::kWgTraceWaves; ++i) {
-          const uint64_t* r = &h[size_t(4 * i)];
-          if (!(r[0] >> 63)) continue;
-          std::fprintf(f, "%d,%llu,%llu,%llu,%llu,%llu,%llu,%d,%d\n", l,
-                       (unsigned long long)((r[0] & ~(1ull << 63)) >> 8), (unsigned long long)(r[0] & 255),
-                       (unsigned long long)(r[1] >> 32), (unsigned long long)(r[1] & 0xFFFFFFFFull),
-                       (unsigned long long)r[2], (unsigned long long)r[3], l ? a.T : pair_T_, int(linkable));
-        }
-        HIP_CHECK(hipFree(pair_trace_[l]));
-        pair_trace_[l] = nullptr;
+    return trace_buf_[which];
+  }
+  void trace_end(const BlockArgs& a, int which, bool linked) {
+    if (which < int(trace_pair_)) return;
+    join_streams();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    std::FILE* f = std::fopen(trace_path_.c_str(), "w");
+    GOL_REQUIRE(f != nullptr, "GOL_WG_TRACE: cannot open " + trace_path_);
+    std::fprintf(f, trace_pair_ ? "launch,block,wave,xcc_id,hw_id,t_start,t_end,T,linked\n"
+                                : "block,wave,xcc_id,hw_id,t_start,t_end,T,rows\n");
+    std::vector<uint64_t> h(size_t(hipk::kWgTraceWaves) * 4);
+    for (int l = 0; l <= which; ++l) {
+      HIP_CHECK(hipMemcpy(h.data(), trace_buf_[l], kTraceBytes, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < hipk::kWgTraceWaves; ++i) {
+        const uint64_t* r = &h[size_t(4 * i)];
+        if (!(r[0] >> 63)) continue;
+        if (trace_pair_) std::fprintf(f, "%d,", l);
+        std::fprintf(f, "%llu,%llu,%llu,%llu,%llu,%llu,%d,%lld\n", (unsigned long long)((r[0] & ~(1ull << 63)) >> 8),
+                     (unsigned long long)(r[0] & 255), (unsigned long long)(r[1] >> 32),
+                     (unsigned long long)(r[1] & 0xFFFFFFFFull), (unsigned long long)r[2], (unsigned long long)r[3],
+                     l < which ? trace_T_ : a.T, trace_pair_ ? (long long)linked : (long long)(a.row_hi - a.row_lo));
       }
-      std::fclose(f);
+      HIP_CHECK(hipFree(trace_buf_[l]));
+      trace_buf_[l] = nullptr;
     }
-    return drift;
+    std::fclose(f);
   }
   void check_device_errors() override {
-    const uint32_t e = __atomic_load_n(err_host_, __ATOMIC_ACQUIRE);
+    uint32_t* const err = mail_host_->err;
+    const uint32_t e = __atomic_load_n(err, __ATOMIC_ACQUIRE);
     if (e != 0) {
-      *err_host_ = 0;
-      const std::string diag = e == 2 ? " [flag " + std::to_string(err_host_[3]) + " read " +
-                                            std::to_string(err_host_[1]) + ", expected " +
-                                            std::to_string(err_host_[2]) + "]"
+      err[0] = 0;
+      const std::string diag = e == 2 ? " [flag " + std::to_string(err[3]) + " read " + std::to_string(err[1]) +
+                                            ", expected " + std::to_string(err[2]) + "]"
                                       : "";
       fail(std::string(e == 2   ? "life_group kernel (chained groups): a wave gave up waiting for the group below" + diag
                        : e == 3 ? "life_group kernel (linked launches): a group gave up waiting for the previous "
@@ -984,7 +931,7 @@ class HipBackend final : public Backend {
     }
   }
   void fill_periodic(void* buf, const TileGeom& g, bool cols, bool rows) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     auto* p = static_cast<uint8_t*>(buf);
@@ -995,7 +942,7 @@ class HipBackend final : public Backend {
     HIP_CHECK(hipGetLastError());
   }
   void fill_cols_rows(void* buf, const TileGeom& g, int64_t r0, int64_t n, void* stream) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_fill_cols_rows(static_cast<uint8_t*>(buf), g, r0, n, stream ? static_cast<hipStream_t>(stream) : stream_);
@@ -1026,7 +973,7 @@ class HipBackend final : public Backend {
   // Host <-> tile transfers go through a bounded device staging buffer so a
   // 32768^2 (1 GiB) or larger grid never needs a second full-size copy.
   void load_owned(void* buf, const TileGeom& g, const uint8_t* cells, int64_t ld) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     const int64_t chunk = rows_per_chunk(g);
@@ -1056,7 +1003,7 @@ class HipBackend final : public Backend {
   }
   void init_random(void* buf, const TileGeom& g, uint64_t seed, double density, int64_t grow0,
                    int64_t gcol0) override {
-    quiet_.prev.T = 0;
+    quiet_invalidate();
     join_streams();
     GOL_ON_DEVICE();
     hipk::launch_init_random(static_cast<uint8_t*>(buf), g, seed, density_thresh(density), grow0, gcol0,
@@ -1106,13 +1053,7 @@ class HipBackend final : public Backend {
     GOL_REQUIRE(d == dev_, std::string("GOL_CHECK_DEVICE: ") + where + " runs on device " + std::to_string(d) +
                                ", backend owns device " + std::to_string(dev_));
   }
-  void check_ptr(const void* p, const char* what) const {
-    if (!p) return;
-    hipPointerAttribute_t at{};
-    HIP_CHECK(hipPointerGetAttributes(&at, p));
-    GOL_REQUIRE(at.device == dev_, std::string("GOL_CHECK_DEVICE: ") + what + " lives on device " +
-                                       std::to_string(at.device) + ", backend owns device " + std::to_string(dev_));
-  }
+  void check_ptr(const void* p, const char* what) const { check_on_device(dev_, p, what); }
 
   int dev_;
   bool check_dev_ = false;  // GOL_CHECK_DEVICE
@@ -1135,17 +1076,18 @@ class HipBackend final : public Backend {
   int numa_cpus_ = 0;      // CPUs it may run on there
   hipk::LifeTuning tune_;
   hipStream_t comm_ = nullptr;
-  // chain_mem: chained groups' flags, slots; linked launches' 3 x completion words.
-  // 5, 6: the skipping kernel's tile-word maps; 7: its counters.
-  void* chain_[8] = {};
-  size_t chain_bytes_[8] = {};
+  hipk::Scratch scratch_;   // chained groups, linked launches and the skipping kernel's device words
   hipk::QuietState quiet_;  // quiet-tile skipping (BlockArgs::quiet)
   QuietTuning quiet_tune_;
-  int64_t quiet_tiles_ = 0;  // tiles launched by the skipping kernel
+  // Launch census: run_block launches by the path launch_life_block reports,
+  // and the tiles of the skipping ones.
+  struct {
+    int64_t launches[hipk::kLaunchPaths] = {};
+    int64_t quiet_tiles = 0;
+  } census_;
   hipk::LinkState link_;  // linked launches (GOL_LINK)
   bool link_on_ = false;  // every eligible launch (GOL_LINK=1)
   int link_mode_ = -1;
-  uint32_t chain_seq_ = 0;
   // Boundary trigger: cumulative device counter, increments expected so
   // far, and the target of the last armed launch (0: none pending).
   unsigned long long* trigger_counter() {
@@ -1162,7 +1104,6 @@ class HipBackend final : public Backend {
   unsigned long long* trigger_mem_ = nullptr;
   uint64_t trigger_total_ = 0, trigger_target_ = 0;
   bool trigger_ok_ = false;
-  int chain_mode_ = 0;  // GOL_CHAIN: 0 off, 1 on, -1 autotuned per launch shape
   bool tune_log_ = false;
   std::map<TuneKey, TuneStats> tuned_;
   std::deque<Pending> pending_;  // timed trial launches not collected yet
@@ -1175,16 +1116,50 @@ class HipBackend final : public Backend {
   int64_t trace_at_ = -1;
   std::string trace_path_;
   bool trace_pair_ = false;
-  uint64_t* pair_trace_[2] = {nullptr, nullptr};
-  int pair_T_ = 0;
+  static constexpr size_t kTraceBytes = size_t(hipk::kWgTraceWaves) * 4 * sizeof(uint64_t);
+  uint64_t* trace_buf_[2] = {nullptr, nullptr};  // wave records of the traced launch (pair: and the next)
+  int trace_T_ = 0;                              // T of the (first) traced launch
   hipEvent_t tail_[2] = {nullptr, nullptr};  // poll_side(): the compute streams' tails
   bool capturing_ = false;                    // between capture_begin and capture_end
   void* stage_ = nullptr;
   int64_t stage_bytes_ = 0;
-  uint32_t* err_host_ = nullptr;
+  hipk::Mailbox* mail_host_ = nullptr;  // the kernels' error and report words, and their device alias
+  hipk::Mailbox* mail_dev_ = nullptr;
 };
 
 }  // namespace
+
+namespace hipk {
+
+uint32_t* Scratch::get(Slot slot, size_t bytes) {
+  static constexpr struct {
+    const char* name;
+    bool zeroed;
+  } kSlot[kSlots] = {{"chain flags", true},  {"chain slots", false}, {"link words A", true},  {"link words B", true},
+                     {"link words C", true}, {"quiet map A", true},  {"quiet map B", true},   {"quiet counters", true}};
+  void*& buf = buf_[slot];
+  if (bytes > bytes_[slot]) {
+    for (hipStream_t s : streams_)  // earlier launches may still use it
+      if (s) HIP_CHECK(hipStreamSynchronize(s));
+    bytes_[slot] = 0;
+    if (buf) HIP_CHECK(hipFree(buf));
+    buf = nullptr;
+    HIP_CHECK(hipMalloc(&buf, bytes));
+    if (kSlot[slot].zeroed) HIP_CHECK(hipMemsetAsync(buf, 0, bytes, streams_[0]));  // ordered before the launch
+    bytes_[slot] = bytes;
+  }
+  if (check_dev_ >= 0) check_on_device(check_dev_, buf, kSlot[slot].name);
+  return static_cast<uint32_t*>(buf);
+}
+
+void Scratch::release() {
+  for (void*& b : buf_) {
+    if (b) hipFree(b);
+    b = nullptr;
+  }
+}
+
+}  // namespace hipk
 
 std::vector<Rule> hip_rules() { return hipk::life_block_rules(); }
 

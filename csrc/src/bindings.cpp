@@ -153,6 +153,7 @@ PYBIND11_MODULE(_gol, m) {
 
   py::class_<Backend, std::shared_ptr<Backend>>(m, "Backend")
       .def("name", &Backend::name)
+      .def("launch_paths", &Backend::launch_paths)
       .def("tuning", &Backend::tuning, py::return_value_policy::copy)
       .def("is_device", &Backend::is_device)
       .def("device", &Backend::device)

@@ -265,6 +265,7 @@ class Simulation:
                                  "skip": self._eng.quiet_blocks_skip},
                 "quiet_waves_launched": self._eng.quiet_waves_launched,
                 "quiet_waves_skipped": self._eng.quiet_waves_skipped,
+                "launch_paths": dict(self.backend.launch_paths()),
                 "tuning": self.tuning(), "tuning_changed": self.tuning_changed()}
 
     def tuning(self) -> dict[str, str]:

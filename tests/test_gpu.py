@@ -217,6 +217,9 @@ def test_chained_groups_vs_torch(gpu, tune, W, H, xlane, tmax, layout):
         sim.load(g)
         sim.advance(gens)
         assert (sim.tile() == want).all(), target
+        # Every parametrisation and wave target here chains; the cells alone
+        # cannot tell.
+        assert sim.describe()["launch_paths"]["chained"] > 0, target
 
 
 def test_chain_autotuning_is_exact(gpu, tune, capfd):
@@ -241,7 +244,8 @@ def test_chain_autotuning_is_exact(gpu, tune, capfd):
 @pytest.mark.parametrize("graphs", ["off", "on"])
 def test_chained_groups_termination_and_row_strips(gpu, tune, graphs):
     """Exact Generations with chained groups, in graph capture (where the
-    chain is off) and on 1x4 row-strip subdomains of one GPU."""
+    chain is off: no captured launch chains or links) and on 1x4 row-strip
+    subdomains of one GPU."""
     tune["chain"] = "1"
     tune["target_waves"] = "100000"
     grid = np.zeros((1024, 512), dtype=np.uint8)
@@ -249,15 +253,45 @@ def test_chained_groups_termination_and_row_strips(gpu, tune, graphs):
     grid[500:500 + H, 200:200 + W] = random_grid(W, H, seed, density)
     ref, rgens, _ = reference_run(grid)
     for layout in ("bits", "u8"):
-        out, rep = simulate(grid, 1000, engine="hip", layout=layout, tmax=16, graphs=graphs)
+        sim = Simulation(LifeConfig(512, 1024, gen_limit=1000, layout=layout, tmax=16, graphs=graphs), engine="hip")
+        sim.load(grid)
+        rep = sim.run()
         assert rep.generations == rgens, layout
-        assert (out == ref).all(), layout
+        assert (sim.tile() == ref).all(), layout
+        if graphs == "on":
+            paths = sim.describe()["launch_paths"]
+            assert rep.graph_launches > 0 and paths["chained"] == 0 and paths["linked"] == 0, (layout, paths)
     grp = InProcessGroup(LifeConfig(512, 1024, decomp="1x4", tmax=16, epoch=64, poll_gens=64, graphs=graphs,
                                     tune=tune), 4, engine="hip")
     grp.load(grid)
     reps = grp.run()
     assert {r.generations for r in reps} == {rgens}
     assert (grp.gather() == ref).all()
+
+
+@pytest.mark.parametrize("extra,path", [({"chain": "1"}, "chained"), ({"link": "1", "chain": "-1"}, "linked")])
+def test_refused_launch_leaves_the_backend_as_it_was(gpu, tune, extra, path):
+    """A launch the host refuses after the backend has prepared it (no kernel
+    is compiled for a temporal block of 5 generations; nothing reaches the
+    device) changes nothing: the simulation goes on to the oracle's cells, and
+    takes the launch paths of one that was never refused - chained groups, resp.
+    linked launches, among them."""
+    W, H, gens = 2048, 333, 43
+    tune.update(extra, row_ring="0")
+    g = random_grid(W, H, 5)
+    want = life_step_torch(g, gens, device="cuda")
+    sims = [Simulation(LifeConfig(W, H, gen_limit=gens, layout="bits", tmax=16, tune=tune), engine="hip")
+            for _ in range(2)]
+    for sim in sims:
+        sim.load(g)
+    Dv = sims[0].describe()["halo_rows"]
+    with pytest.raises(RuntimeError, match="unsupported temporal block size"):
+        sims[0].native_engine.step_block(5, Dv, Dv + H)
+    for sim in sims:
+        sim.advance(gens)
+        assert (sim.tile() == want).all()
+    paths = [sim.describe()["launch_paths"] for sim in sims]
+    assert paths[0] == paths[1] and paths[0][path] > 0, paths
 
 
 @pytest.mark.parametrize("words", [79, 93, 136, 1024])

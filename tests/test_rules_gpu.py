@@ -175,6 +175,7 @@ def test_rule_runs_are_never_linked(gpu, tune):
         d = sim.describe()
         assert d["rule"] == rule and f"rule {rule}" in d["kernel"]
         assert rep.linked_launches == 0, extra
+        assert d["launch_paths"]["chained"] == 0 and d["launch_paths"]["linked"] == 0, (extra, d["launch_paths"])
         assert (sim.tile() == want).all(), extra
 
 
