@@ -53,7 +53,7 @@ bench: build
 
 selftest-asan:
 	$(PYTHON) game-of-life-in-parallel-mpi-openmp-cuda_amd/native_build.py --selftest address
-	./bin/gol_selftest_address
+	ASAN_OPTIONS=detect_leaks=1 ./bin/gol_selftest_address
 
 selftest-tsan:
 	$(PYTHON) game-of-life-in-parallel-mpi-openmp-cuda_amd/native_build.py --selftest thread

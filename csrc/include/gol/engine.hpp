@@ -146,7 +146,7 @@ class Engine {
   // The tile the temporal blocks run on: geom(), or its bit-word image when
   // the byte layout computes on bit words (via_bits(); the byte tile then has
   // no halos).
-  const TileGeom& compute_geom() const { return via_bits_ ? gb_ : g_; }
+  const TileGeom& compute_geom() const { return tile_geom(via_bits_); }
   int rank() const { return rank_; }
   Extent rows() const { return dec_.rows(rank_); }
   Extent cols() const { return dec_.cols(rank_); }
@@ -239,6 +239,91 @@ class Engine {
   void step_block(int T, int64_t row_lo, int64_t row_hi);
 
  private:
+  // A device (or pinned-host) allocation owned by the engine: released
+  // through the backend it came from when the handle goes out of scope, so a
+  // constructor that throws leaves nothing allocated.
+  template <class T = void>
+  class Owned {
+   public:
+    Owned() = default;
+    Owned(Backend* be, void* p, bool host = false) : be_(be), p_(static_cast<T*>(p)), host_(host) {}
+    Owned(Owned&& o) noexcept : be_(o.be_), p_(o.p_), host_(o.host_) { o.p_ = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+      if (this != &o) {
+        reset();
+        be_ = o.be_, p_ = o.p_, host_ = o.host_;
+        o.p_ = nullptr;
+      }
+      return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() {
+      if (p_) host_ ? be_->release_host(p_) : be_->release(p_);
+      p_ = nullptr;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+
+   private:
+    Backend* be_ = nullptr;
+    T* p_ = nullptr;
+    bool host_ = false;
+  };
+  // A timed span between two Backend::timing_mark marks, tagged with its
+  // trial slot or its phase.
+  struct Span {
+    int kind;
+    void* a;
+    void* b;
+  };
+  // Bookkeeping of a run-time A/B trial (the overlap trial over epochs, the
+  // poll placement trial over poll windows): spans of two alternating slots
+  // timed on the compute stream, one of them open at a time.  The policy -
+  // which slot comes next, when to decide and on what - stays with its trial.
+  struct Trial {
+    explicit Trial(Backend* b) : be(b) {}
+    Backend* be;
+    void* open = nullptr;  // start mark of the open span
+    int slot = -1;         // its slot (-1: a warm-up span, not recorded)
+    std::vector<Span> spans;
+    int counts[2] = {0, 0};
+
+    // Ends the open span (if any) at a mark taken now: recorded under its
+    // slot, or both marks released when it was a warm-up.
+    void close();
+    void begin(int s) {
+      open = be->timing_mark(nullptr);
+      slot = s;
+    }
+    bool full(int s) const;  // kAutoTrials spans of slot s are in
+    // Medians of the two slots' spans, MAX over ranks (the slowest rank
+    // decides; every rank gets the same values), in ms; releases the spans.
+    // `dev` is device scratch for two words.
+    void medians(Transport* tr, uint32_t* dev, double out[2]);
+    void drop_open();  // a span does not continue into the next run
+    void release();
+  };
+  // One of the two images of the tile: the storage tile (bytes, or the bit
+  // layout's words) or the bit-word image of a byte tile.  `par` is the parity
+  // of the buffer that holds the current generation.
+  struct Tile {
+    const TileGeom& g;
+    int& par;
+    void* buf[2];
+    void* cur() const { return buf[par]; }
+    void* next() const { return buf[par ^ 1]; }
+  };
+  const TileGeom& tile_geom(bool bits) const { return bits ? gb_ : g_; }
+  Tile tile(bool bits) {
+    if (bits) return {gb_, bpar_, {bit_scratch(0), bit_scratch(1)}};
+    return {g_, cur_, {buf_[0], buf_[1]}};
+  }
+  // The tile the temporal blocks alternate over during a run, and the one
+  // that holds the state now (the bit image stays the state after a run until
+  // the byte tile is read, sync_bytes).
+  Tile compute_tile() { return tile(via_bits_); }
+  Tile state_tile() { return tile(bits_live_); }
+
   struct Poll {
     int64_t from = 0, to = 0;
     void* ev = nullptr;
@@ -246,6 +331,8 @@ class Engine {
   RunResult run_impl(int64_t limit, bool stop_early);
   Poll poll_issue(int64_t from, int64_t to);
   bool poll_check(Poll& p, int64_t* first_unchanged);
+  // Offset of generation from + 1's flag in the flag window (device and mirror).
+  int64_t flag_offset(int64_t from) const { return from + 1 - flags_base_; }
   int pick_T(int64_t remaining) const;
   // One temporal block in <in> -> <out> for generations (gen_base, gen_base+T];
   // returns the frame drift of the launch (cells).
@@ -255,12 +342,13 @@ class Engine {
   // cone at top issue priority (engine.cpp).
   void hot_block(void* in, void* out, const TileGeom& g, int T, int64_t row_lo, int64_t row_hi, int64_t d);
   void add_drift(int64_t cells);
+  // Phase-timed Backend::fill_periodic on the compute stream.
+  void fill(void* buf, const TileGeom& g, bool cols, bool rows);
   void exchange_columns(void* buf, const TileGeom& g);
   std::vector<P2POp> row_ops(void* buf, const TileGeom& g) const;
   void halo_exchange_on(void* buf, const TileGeom& g);
-  // Byte layout on bit words (EngineConfig::u8_compute = 1): one epoch on
-  // the bit tile, and the per-run pack / unpack of the byte tile.
-  void epoch_via_bits(int64_t d, bool sent_ahead);
+  // Byte layout on bit words (EngineConfig::u8_compute = 1): the per-run
+  // pack / unpack of the byte tile; the epochs run on compute_tile().
   void pack_bits();
   void unpack_bits();
   void sync_bytes();  // unpack a live bit image into the byte tile (pack_bits in engine.cpp)
@@ -294,20 +382,20 @@ class Engine {
   int rank_ = 0;
   TileGeom g_;
   int D_ = 0, tmax_ = 0, poll_gens_ = 0;
-  void* buf_[2] = {nullptr, nullptr};
+  Owned<> buf_[2];
   int cur_ = 0;
-  uint32_t* flags_ = nullptr;      // device: changed[t - flags_base_]
-  uint32_t* flags_host_ = nullptr; // pinned mirror
+  Owned<uint32_t> flags_;       // device: changed[t - flags_base_]
+  Owned<uint32_t> flags_host_;  // pinned mirror
   int64_t flags_base_ = 0, flags_len_ = 0;
-  uint32_t* alive_dev_ = nullptr;
-  void* colbuf_[4] = {nullptr, nullptr, nullptr, nullptr};  // send W, send E, recv W, recv E
+  Owned<uint32_t> alive_dev_;
+  Owned<> colbuf_[4];  // send W, send E, recv W, recv E
   bool trigger_ = false;             // boundary-triggered sends (overlap = 3)
   int64_t triggered_sends_ = 0;
   bool send_next_ = false;           // the current epoch is followed by another one in this run
-  bool rows_pending_ = false;        // halo rows of buf_[cur_] were sent by the last block
+  bool rows_pending_ = false;        // halo rows of the compute tile's current buffer were sent by the last block
   int64_t boundary_sends_ = 0;      // exchanges sent from an epoch's last block (RunResult::overlapped)
   bool use_graphs_ = false, capturing_ = false;
-  int64_t* gen_dev_ = nullptr;        // device: (epoch start - flags_base_) for graph replays
+  Owned<int64_t> gen_dev_;            // device: (epoch start - flags_base_) for graph replays
   int64_t epoch_start_ = 0;
   // Captured epochs, keyed by graph_key(): the parity of the buffer pair the
   // epochs alternate over and, for the byte layout on bit words, the byte
@@ -328,9 +416,9 @@ class Engine {
   bool rows_ring_ = false;    // row halos are second mappings of the owned rows (Backend::row_ring_halo)
   std::string ring_fallback_;  // alloc_row_ring's error when the ring fell back to fills
   bool link_ = false;         // blocks may run linked (Backend::KernelChoice::link; ring tiles only)
-  bool via_bits_ = false;    // byte layout computed on bit words (epoch_via_bits)
+  bool via_bits_ = false;    // byte layout computed on bit words (compute_tile() is the bit image)
   TileGeom gb_;              // the tile in the bit layout (same rows, halos, words)
-  void* bitbuf_[2] = {nullptr, nullptr};  // own bit scratch when the spare byte buffer cannot hold it
+  Owned<> bitbuf_[2];        // own bit scratch when the spare byte buffer cannot hold it
   int bpar_ = 0;             // bit_scratch(bpar_) holds the current generation during a run
   bool bits_live_ = false;   // ... and after it, until the byte tile is read (sync_bytes)
   bool poll_side_ = false;   // termination polls reduce on the comm stream (Transport::side_reduce)
@@ -346,37 +434,21 @@ class Engine {
   // Overlap auto trial.
   bool auto_overlap_ = false;       // trial still running
   bool auto_decided_ = false;
-  int auto_sched_ = 0;              // trial slot of the current epoch: 0 plain, 1 trigger
+  int auto_sched_ = 0;              // trial slot of the current epoch: 0 plain, 1 trigger, -1 warm-up
   int64_t auto_full_epochs_ = 0;    // full epochs seen so far
-  void* auto_open_ = nullptr;       // start mark of the current epoch
-  int auto_open_sched_ = -1;        // its schedule (-1: not a trial epoch)
-  struct AutoSpan {
-    int sched;
-    void* a;
-    void* b;
-  };
-  std::vector<AutoSpan> auto_spans_;
-  int auto_counts_[2] = {0, 0};
+  Trial otrial_{be_};
   double auto_ms_[2] = {-1, -1};
-  void trial_medians(std::vector<AutoSpan>& spans, double out[2]);
-  // Poll placement trial (tuning side_poll = -1, poll_trial_step).
+  // Poll placement trial (tuning side_poll = -1, poll_trial_step): slot 0
+  // joined, 1 side.
   bool poll_trial_ = false, poll_decided_ = false;
   int64_t ptrial_polls_ = 0;
-  int ptrial_mode_ = -1;            // placement of the open window: 0 joined, 1 side, -1 warm-up
-  void* ptrial_open_ = nullptr;
-  std::vector<AutoSpan> ptrial_spans_;
-  int ptrial_counts_[2] = {0, 0};
+  Trial ptrial_{be_};
   double poll_ms_[2] = {-1, -1};
   bool ptrial_verify_ = false;      // checking a side decision on consecutive side windows
   double poll_side_steady_ms_ = -1;
   // Phase timing.
   bool phase_timing_ = false;
-  struct PhaseSpan {
-    int phase;
-    void* a;
-    void* b;
-  };
-  std::vector<PhaseSpan> phase_spans_;
+  std::vector<Span> phase_spans_;
 };
 
 }  // namespace gol

@@ -130,6 +130,7 @@ class CpuBackend final : public Backend {
     ring_ = !ring.empty() && ring != "0";
     ring_fail_ = ring == "fail";  // tests: the mapping fails after the size check
     trigger_ = t.on("cpu_trigger");
+    fault_alloc_ = t.i("fault_alloc");
   }
   // GOL_CPU_TRIGGER=1: the engine's boundary-trigger schedule (overlap =
   // trigger) on the host.  Every operation completes in program order, so the
@@ -196,7 +197,9 @@ class CpuBackend final : public Backend {
   bool is_device() const override { return false; }
 
   void* alloc(size_t bytes) override {
-    void* p = std::calloc(bytes ? bytes : 1, 1);
+    // fault_alloc=N: this backend's N-th allocation fails (tests of what the caller then holds).
+    const bool fault = fault_alloc_ > 0 && ++allocs_ == fault_alloc_;
+    void* p = fault ? nullptr : std::calloc(bytes ? bytes : 1, 1);
     GOL_REQUIRE(p, "host allocation of " + std::to_string(bytes) + " bytes failed");
     return p;
   }
@@ -269,6 +272,7 @@ class CpuBackend final : public Backend {
   bool ring_ = false;      // GOL_CPU_RING
   bool ring_fail_ = false;  // GOL_CPU_RING=fail
   bool trigger_ = false;    // GOL_CPU_TRIGGER
+  int fault_alloc_ = 0, allocs_ = 0;  // GOL_FAULT_ALLOC: alloc() number fault_alloc_ fails
   bool armed_ = false;      // the last run_block carried BlockArgs::trigger
   std::mutex ring_mu_;
   std::map<void*, size_t> rings_;  // row rings: base -> mapped bytes

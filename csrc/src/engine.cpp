@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <thread>
 
 #include "gol/trace.hpp"
@@ -101,7 +102,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // backend cannot build them after all (address space, driver), the tile
   // falls back to plain buffers with periodic fills.
   int ring_dv = 0;
-  void* ring_bufs[2] = {nullptr, nullptr};
+  Owned<> ring_bufs[2];
   if (dec_.Px == 1 && dec_.Py == 1 && !cfg_.self_exchange && !rows_wrapped_) {
     const TileGeom probe = TileGeom::make(cl, r.size(), c.size(), 0, hw);
     ring_dv = be_->row_ring_halo(probe.H, probe.pitch, tmax_);
@@ -117,14 +118,13 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
     if (ring_dv > 0) {
       const TileGeom gr = TileGeom::make(cl, r.size(), c.size(), ring_dv, hw);
       try {
-        for (auto& b : ring_bufs) {
-          b = be_->alloc_row_ring(gr);
+        Owned<> tried[2];  // a ring that came before a failure goes with this scope
+        for (auto& b : tried) {
+          b = Owned<>(be_, be_->alloc_row_ring(gr));
           GOL_REQUIRE(b, "the backend returned no ring");
         }
+        for (int i = 0; i < 2; ++i) ring_bufs[i] = std::move(tried[i]);
       } catch (const std::exception& e) {
-        for (auto& b : ring_bufs)
-          if (b) be_->release(b);
-        ring_bufs[0] = ring_bufs[1] = nullptr;
         ring_dv = 0;
         ring_fallback_ = e.what();
         std::fprintf(stderr, "gol: WARNING: row ring unavailable (%s); periodic row fills instead\n", e.what());
@@ -151,26 +151,27 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // (latency-bound), so poll half as often; a stop is still exact and at most
   // two windows late.
   poll_gens_ = cfg_.poll_gens > 0 ? cfg_.poll_gens : (tr_->size() > 1 || cfg_.self_exchange) ? 512 : 256;
+  // The rings are the compute tile's buffers (each owned once: moved).
   if (rows_ring_ && !via_bits_) {
-    for (int i = 0; i < 2; ++i) buf_[i] = ring_bufs[i];
+    for (int i = 0; i < 2; ++i) buf_[i] = std::move(ring_bufs[i]);
   } else {
-    for (auto& b : buf_) b = be_->alloc(size_t(g_.bytes()));
+    for (auto& b : buf_) b = Owned<>(be_, be_->alloc(size_t(g_.bytes())));
   }
   if (via_bits_) {
     // The bit words live in the spare byte buffer (about an eighth of its
     // size per parity) unless a small tile's halo rows or pitch rounding do
     // not leave room, or they form a row ring.
     if (rows_ring_) {
-      for (int i = 0; i < 2; ++i) bitbuf_[i] = ring_bufs[i];
+      for (int i = 0; i < 2; ++i) bitbuf_[i] = std::move(ring_bufs[i]);
     } else if (2 * gb_.bytes() > g_.bytes()) {
-      for (auto& b : bitbuf_) b = be_->alloc(size_t(gb_.bytes()));
+      for (auto& b : bitbuf_) b = Owned<>(be_, be_->alloc(size_t(gb_.bytes())));
     }
   }
-  alive_dev_ = static_cast<uint32_t*>(be_->alloc(64));
+  alive_dev_ = Owned<uint32_t>(be_, be_->alloc(64));
   if (dec_.Px > 1) {
-    const TileGeom& gc = via_bits_ ? gb_ : g_;  // the tile whose halos are exchanged
+    const TileGeom& gc = compute_geom();  // the tile whose halos are exchanged
     size_t n = size_t(gc.span_bytes(32 * int64_t(gc.hw)) * gc.H);
-    for (auto& b : colbuf_) b = be_->alloc(n);
+    for (auto& b : colbuf_) b = Owned<>(be_, be_->alloc(n));
   }
   // Boundary-triggered sends (overlap = 3; last_block_trigger): row strips
   // on a backend that can count boundary groups done.  Byte tiles on bit
@@ -180,7 +181,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   watchdog_s_ = cfg_.watchdog_s > 0 ? cfg_.watchdog_s : cfg_.tune.f("watchdog_s") > 0 ? cfg_.tune.f("watchdog_s") : 900.0;
   use_graphs_ = cfg_.graphs != 0 && be_->supports_graphs() && tr_->capturable() &&
                 (cfg_.graphs > 0 || tr_->size() == 1);
-  if (use_graphs_) gen_dev_ = static_cast<int64_t*>(be_->alloc(sizeof(int64_t)));
+  if (use_graphs_) gen_dev_ = Owned<int64_t>(be_, be_->alloc(sizeof(int64_t)));
   if (use_graphs_) trigger_ = false;  // captured epochs stay on one stream
   // Overlap auto: measure both schedules on the real ranks (see auto_choose);
   // the one-GPU rehearsal has no xGMI latency in it, so on a multi-GPU node
@@ -227,7 +228,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
     quiet_.scout = qt.scout;
     quiet_.on = qt.on;
     quiet_.off = qt.off;
-    be_->quiet_prepare(via_bits_ ? gb_ : g_);
+    be_->quiet_prepare(compute_geom());
   }
   gen_ = cfg_.start_gen;
 }
@@ -240,28 +241,14 @@ void Engine::release_graphs() {
 }
 
 Engine::~Engine() {
+  // Graphs and timing marks; the buffers go with their handles.
   release_graphs();
-  for (auto* spans : {&auto_spans_, &ptrial_spans_})
-    for (auto& sp : *spans) {
-      be_->timing_release(sp.a);
-      be_->timing_release(sp.b);
-    }
-  if (ptrial_open_) be_->timing_release(ptrial_open_);
-  if (auto_open_) be_->timing_release(auto_open_);
+  otrial_.release();
+  ptrial_.release();
   for (auto& sp : phase_spans_) {
     be_->timing_release(sp.a);
     be_->timing_release(sp.b);
   }
-  if (gen_dev_) be_->release(gen_dev_);
-  for (auto& b : buf_)
-    if (b) be_->release(b);
-  for (auto& b : colbuf_)
-    if (b) be_->release(b);
-  for (auto& b : bitbuf_)
-    if (b) be_->release(b);
-  if (flags_) be_->release(flags_);
-  if (flags_host_) be_->release_host(flags_host_);
-  if (alive_dev_) be_->release(alive_dev_);
 }
 
 void Engine::load_cells(const uint8_t* cells, int64_t ld) {
@@ -295,7 +282,7 @@ void Engine::store_rows(uint8_t* cells, int64_t ld, int64_t r0, int64_t n, bool 
   // A view of the band: the same pitch and halos, its first owned row at r0.
   TileGeom v = g_;
   v.H = n;
-  be_->store_owned(static_cast<uint8_t*>(buf_[cur_]) + r0 * g_.pitch, v, cells, ld, ascii);
+  be_->store_owned(static_cast<uint8_t*>(buf_[cur_].get()) + r0 * g_.pitch, v, cells, ld, ascii);
 }
 
 void Engine::init_random(uint64_t seed, double density) {
@@ -319,8 +306,8 @@ void Engine::normalize() {
 
 int64_t Engine::alive_count() {
   be_->synchronize();
-  if (bits_live_) return be_->alive_count(bit_scratch(bpar_), gb_);
-  return be_->alive_count(buf_[cur_], g_);
+  const Tile s = state_tile();
+  return be_->alive_count(s.cur(), s.g);
 }
 
 int Engine::pick_T(int64_t remaining) const {
@@ -334,21 +321,19 @@ int Engine::pick_T(int64_t remaining) const {
   return 1;
 }
 
-// Phase A of the halo exchange (halo_exchange_on): west / east halo columns
-// of the owned rows, packed into contiguous buffers (RCCL has no strided
-// datatype, unlike the reference's MPI_Type_vector column).
+void Engine::fill(void* buf, const TileGeom& g, bool cols, bool rows) {
+  void* t = phase_begin(nullptr);
+  be_->fill_periodic(buf, g, cols, rows);
+  phase_end(kFill, t, nullptr);
+}
+
+// Phase A of the halo exchange (halo_exchange_on) between ranks (Px > 1):
+// west / east halo columns of the owned rows, packed into contiguous buffers
+// (RCCL has no strided datatype, unlike the reference's MPI_Type_vector column).
 void Engine::exchange_columns(void* buf, const TileGeom& g) {
   auto* base = static_cast<uint8_t*>(buf);
   auto nb = dec_.neighbors(rank_);
   const int64_t H = g.H, pitch = g.pitch;
-  if (dec_.Px == 1) {
-    if (cols_filled_) {
-      void* t = phase_begin(nullptr);
-      be_->fill_periodic(buf, g, /*cols=*/true, /*rows=*/false);
-      phase_end(kFill, t, nullptr);
-    }
-    return;
-  }
   void* t = phase_begin(nullptr);
   const int64_t halo = 32 * int64_t(g.hw);
   const int64_t span = g.span_bytes(halo);
@@ -376,44 +361,36 @@ void Engine::halo_exchange() { halo_exchange_on(buf_[cur_], g_); }
 
 void Engine::halo_exchange_on(void* buf, const TileGeom& g) {
   trace::Range tr("gol.halo_exchange");
-  if (rows_wrapped_ || (rows_ring_ && !cols_filled_)) {
-    // Nothing to move: the kernels read the torus modulo its rows, or the
-    // row halos alias the owned rows.  No stream join either, so linked
-    // launches (GOL_LINK) chain across such epochs.
-    ++exchanges_;
-    return;
-  }
+  ++exchanges_;
+  // Each direction's halos come from this tile's own periodic wrap (a fill,
+  // or nothing where the kernels wrap their reads or the row halos alias the
+  // owned rows: rows_wrapped_ and rows_ring_ are single-rank tiles) or from
+  // the neighbours through the transport.
+  const bool cols_local = dec_.Px == 1, rows_local = dec_.Py == 1 && !cfg_.self_exchange;
+  const bool fill_cols = cols_local && cols_filled_;
+  const bool fill_rows = rows_local && !rows_wrapped_ && !rows_ring_;
+  // Nothing to move: no stream join either, so linked launches (GOL_LINK)
+  // chain across such epochs.
+  if (cols_local && rows_local && !fill_cols && !fill_rows) return;
   be_->join_streams();  // transports enqueue on the compute stream directly
-  if (rows_ring_) {  // the row halos alias the owned rows; only column halos need a fill
-    if (cols_filled_) {
-      void* t = phase_begin(nullptr);
-      be_->fill_periodic(buf, g, /*cols=*/true, /*rows=*/false);
-      phase_end(kFill, t, nullptr);
-    }
-    ++exchanges_;
-    return;
-  }
-  if (dec_.Px == 1 && dec_.Py == 1 && !cfg_.self_exchange) {  // one rank: both periodic fills, one launch
-    void* t = phase_begin(nullptr);
-    be_->fill_periodic(buf, g, /*cols=*/cols_filled_, /*rows=*/true);
-    phase_end(kFill, t, nullptr);
-    ++exchanges_;
+  if (cols_local && rows_local) {  // one rank: its periodic fills in one launch
+    fill(buf, g, fill_cols, fill_rows);
     return;
   }
   // Phase A: west/east halo columns of the owned rows.
-  exchange_columns(buf, g);
+  if (!cols_local)
+    exchange_columns(buf, g);
+  else if (fill_cols)
+    fill(buf, g, /*cols=*/true, /*rows=*/false);
   // Phase B: north/south halo rows over the full padded width.
-  if (dec_.Py == 1 && !cfg_.self_exchange) {
-    void* t = phase_begin(nullptr);
-    be_->fill_periodic(buf, g, /*cols=*/false, /*rows=*/true);
-    phase_end(kFill, t, nullptr);
+  if (rows_local) {
+    fill(buf, g, /*cols=*/false, /*rows=*/true);
   } else {
     void* t = phase_begin(nullptr);
     tr_->exchange(row_ops(buf, g), be_->stream());
     phase_end(kHalo, t, nullptr);
     halo_bytes_ += 2 * g.Dv * g.pitch;
   }
-  ++exchanges_;
 }
 
 // North / south halo rows over the full padded width, Dv rows each way.
@@ -432,34 +409,7 @@ std::vector<P2POp> Engine::row_ops(void* buf, const TileGeom& g) const {
 
 void* Engine::bit_scratch(int i) const {
   if (bitbuf_[i]) return bitbuf_[i];
-  return static_cast<uint8_t*>(buf_[cur_ ^ 1]) + i * gb_.bytes();
-}
-
-// Byte-layout epoch on bit words (run_impl packs the byte tile into
-// bit_scratch(bpar_) when a run starts and unpacks it when the run ends): the
-// halo exchange or fill and every temporal block run on the bit tile, whose
-// per-generation flags are those of the same cells.
-void Engine::epoch_via_bits(int64_t d, bool sent_ahead) {
-  trace::Range tr("gol.epoch_via_bits");
-  if (!sent_ahead) halo_exchange_on(bit_scratch(bpar_), gb_);
-  // A partial epoch's trapezoid starts d rows outside the owned rows; a row
-  // ring's blocks all cover exactly the owned rows (a = Dv - T).
-  const bool full = d == D_;
-  int64_t a = D_ - d;
-  while (d > 0) {
-    const int T = pick_T(d);
-    if (rows_ring_) a = gb_.Dv - T;
-    if (d == T && trigger_ && send_next_ && full)
-      last_block_trigger(bit_scratch(bpar_), bit_scratch(bpar_ ^ 1), gb_, T);
-    else if (trigger_ && send_next_ && full)
-      hot_block(bit_scratch(bpar_), bit_scratch(bpar_ ^ 1), gb_, T, a + T, gb_.R() - a - T, d);
-    else
-      add_drift(launch(bit_scratch(bpar_), bit_scratch(bpar_ ^ 1), gb_, T, a + T, gb_.R() - a - T, gen_));
-    bpar_ ^= 1;
-    gen_ += T;
-    a += T;
-    d -= T;
-  }
+  return static_cast<uint8_t*>(buf_[cur_ ^ 1].get()) + i * gb_.bytes();
 }
 
 // The byte grid <-> its bit-word image in the spare byte buffer: a run packs
@@ -497,29 +447,30 @@ void Engine::run_epoch(int64_t d) {
   rows_pending_ = false;
   // The previous epoch ends here.
   if (auto_overlap_) auto_mark();
-  if (via_bits_) {
-    epoch_via_bits(d, sent_ahead);
-    return;
-  }
-  if (!sent_ahead) halo_exchange();
+  // The halo exchange or fill and every temporal block run on the compute
+  // tile.  For a byte tile on bit words that is its bit image (run_impl packs
+  // the byte tile into it when a run starts; it is unpacked when the byte
+  // tile is next read), whose per-generation flags are those of the same cells.
+  std::optional<trace::Range> tr;
+  if (via_bits_) tr.emplace("gol.epoch_via_bits");
+  const Tile t = compute_tile();
+  if (!sent_ahead) halo_exchange_on(t.cur(), t.g);
   // A partial epoch (d < D) needs only d halo rows: its trapezoid starts d
   // rows outside the owned rows, not D.
-  const bool full = d == D_;
+  const bool hot = trigger_ && send_next_ && d == D_;  // a full epoch of the trigger schedule
   int64_t a = D_ - d;
   while (d > 0) {
     const int T = pick_T(d);
-    if (rows_ring_) a = g_.Dv - T;  // every block covers exactly the owned rows
-    if (d == T && trigger_ && send_next_ && full) {
-      last_block_trigger(buf_[cur_], buf_[cur_ ^ 1], g_, T);
-      cur_ ^= 1;
-      gen_ += T;
-    } else if (trigger_ && send_next_ && full) {
-      hot_block(buf_[cur_], buf_[cur_ ^ 1], g_, T, a + T, g_.R() - a - T, d);
-      cur_ ^= 1;
-      gen_ += T;
-    } else {
-      step_block(T, a + T, g_.R() - a - T);
-    }
+    if (rows_ring_) a = t.g.Dv - T;  // every block covers exactly the owned rows
+    const int64_t lo = a + T, hi = t.g.R() - a - T;
+    if (hot && d == T)
+      last_block_trigger(t.cur(), t.next(), t.g, T);
+    else if (hot)
+      hot_block(t.cur(), t.next(), t.g, T, lo, hi, d);
+    else
+      add_drift(launch(t.cur(), t.next(), t.g, T, lo, hi, gen_));
+    t.par ^= 1;
+    gen_ += T;
     a += T;
     d -= T;
   }
@@ -598,7 +549,7 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
     a.gen_rel = gen_base - epoch_start_ + 1;
   } else {
     a.changed =
-        (flags_ && gen_base + T < flags_base_ + flags_len_ && gen_base >= flags_base_) ? flags_ : nullptr;
+        (flags_ && gen_base + T < flags_base_ + flags_len_ && gen_base >= flags_base_) ? flags_.get() : nullptr;
   }
   a.flags_base = flags_base_;
   a.allow_drift = drift_ok_;
@@ -673,7 +624,7 @@ Engine::Poll Engine::poll_issue(int64_t from, int64_t to) {
   p.to = to;
   const int64_t n = to - from;
   if (n <= 0) return p;
-  uint32_t* dev = flags_ + (from + 1 - flags_base_);
+  uint32_t* dev = flags_ + flag_offset(from);
   // A side stream that waits for the compute streams' tails without joining
   // them: side polls (the reduction on the flags communicator), and on one
   // rank the copy alone (nothing to reduce, poll_copy_side_) - a linked chain
@@ -688,7 +639,7 @@ Engine::Poll Engine::poll_issue(int64_t from, int64_t to) {
     void* t = phase_begin(side);
     // The one-rank RCCL rehearsal reduces too, through its 1-rank communicator.
     if (tr_->size() > 1 || cfg_.self_exchange) tr_->allreduce_max_u32(dev, size_t(n), side);
-    be_->copy_d2h_async_on(flags_host_ + (from + 1 - flags_base_), dev, size_t(n) * sizeof(uint32_t), side);
+    be_->copy_d2h_async_on(flags_host_ + flag_offset(from), dev, size_t(n) * sizeof(uint32_t), side);
     phase_end(kReduce, t, side);
     p.ev = be_->event_record_on(side);
     ++polls_;
@@ -697,7 +648,7 @@ Engine::Poll Engine::poll_issue(int64_t from, int64_t to) {
   be_->join_streams();  // transports enqueue on the compute stream directly
   void* t = phase_begin(nullptr);
   if (tr_->size() > 1) tr_->allreduce_max_u32(dev, size_t(n), be_->stream());
-  be_->copy_d2h_async_on(flags_host_ + (from + 1 - flags_base_), dev, size_t(n) * sizeof(uint32_t), nullptr);
+  be_->copy_d2h_async_on(flags_host_ + flag_offset(from), dev, size_t(n) * sizeof(uint32_t), nullptr);
   phase_end(kReduce, t, nullptr);
   p.ev = be_->event_record_on(nullptr);
   ++polls_;
@@ -732,7 +683,7 @@ bool Engine::poll_check(Poll& p, int64_t* first_unchanged) {
   be_->event_destroy(p.ev);
   p.ev = nullptr;
   be_->check_device_errors();
-  const uint32_t* h = flags_host_ + (p.from + 1 - flags_base_);
+  const uint32_t* h = flags_host_ + flag_offset(p.from);
   for (int64_t i = 0; i < p.to - p.from; ++i)
     if (h[i] == 0) {
       *first_unchanged = p.from + 1 + i;
@@ -787,11 +738,11 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   // (Re)allocate per-generation flags for (start, limit].
   const int64_t need = limit - start + 2;
   if (!flags_ || flags_len_ < need) {
-    if (flags_) be_->release(flags_);
-    if (flags_host_) be_->release_host(flags_host_);
+    flags_.reset();
+    flags_host_.reset();
     flags_len_ = std::max<int64_t>(need, 64);
-    flags_ = static_cast<uint32_t*>(be_->alloc(size_t(flags_len_) * 4));
-    flags_host_ = static_cast<uint32_t*>(be_->alloc_host(size_t(flags_len_) * 4));
+    flags_ = Owned<uint32_t>(be_, be_->alloc(size_t(flags_len_) * 4));
+    flags_host_ = Owned<uint32_t>(be_, be_->alloc_host(size_t(flags_len_) * 4), /*host=*/true);
   }
   flags_base_ = start;
   be_->memset_async(flags_, 0, size_t(flags_len_) * 4);
@@ -828,7 +779,7 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
       // device generation offset, advanced by the graph itself.  Graphs are
       // keyed by the parity of the buffer pair the epochs alternate over and
       // by the addresses baked into them (graph_key).
-      int& cur = via_bits_ ? bpar_ : cur_;
+      int& cur = compute_tile().par;
       const int par = graph_key();
       if (!graph_[par]) {
         const int64_t k0 = launches_;
@@ -885,14 +836,8 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   polled_side_ = false;
   be_->synchronize();
   be_->check_device_errors();
-  if (auto_open_) {  // an auto-trial epoch span does not continue into the next run
-    be_->timing_release(auto_open_);
-    auto_open_ = nullptr;
-  }
-  if (ptrial_open_) {  // nor does a poll-trial window
-    be_->timing_release(ptrial_open_);
-    ptrial_open_ = nullptr;
-  }
+  otrial_.drop_open();  // an auto-trial epoch span does not continue into the next run
+  ptrial_.drop_open();  // nor does a poll-trial window
   if (cfg_.timing_barriers) {
     settle_pending(false);
     tr_->barrier();
@@ -911,10 +856,8 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   collect_phases(res);
   if (found >= 0) {
     res.first_unchanged = found;
-    if (bits_live_)
-      be_->alive_any(bit_scratch(bpar_), gb_, alive_dev_);
-    else
-      be_->alive_any(buf_[cur_], g_, alive_dev_);
+    const Tile s = state_tile();
+    be_->alive_any(s.cur(), s.g, alive_dev_);
     if (tr_->size() > 1) tr_->allreduce_max_u32(alive_dev_, 1, be_->stream());
     uint32_t alive = 0;
     be_->copy_d2h(&alive, alive_dev_, 4);
@@ -945,33 +888,36 @@ void Engine::auto_choose(bool full_epoch) {
 }
 
 void Engine::auto_mark() {
-  if (auto_open_) {
-    void* end = be_->timing_mark(nullptr);
-    if (auto_open_sched_ >= 0) {
-      auto_spans_.push_back({auto_open_sched_, auto_open_, end});
-      ++auto_counts_[auto_open_sched_];
-    } else {
-      be_->timing_release(auto_open_);
-      be_->timing_release(end);
-    }
-    auto_open_ = nullptr;
-  }
-  if (auto_counts_[0] >= kAutoTrials && auto_counts_[1] >= kAutoTrials) {
+  otrial_.close();
+  if (otrial_.full(0) && otrial_.full(1)) {
     auto_decide();
     return;
   }
-  auto_open_ = be_->timing_mark(nullptr);
-  auto_open_sched_ = auto_sched_;
+  otrial_.begin(auto_sched_);
 }
 
-// Medians of two schedules' timed spans, MAX over ranks (the slowest rank
-// decides; every rank gets the same values), in ms; releases the spans.
-void Engine::trial_medians(std::vector<AutoSpan>& spans, double out[2]) {
+// ---- trial bookkeeping ------------------------------------------------------
+void Engine::Trial::close() {
+  if (!open) return;
+  void* end = be->timing_mark(nullptr);
+  if (slot >= 0) {
+    spans.push_back({slot, open, end});
+    ++counts[slot];
+  } else {
+    be->timing_release(open);
+    be->timing_release(end);
+  }
+  open = nullptr;
+}
+
+bool Engine::Trial::full(int s) const { return counts[s] >= kAutoTrials; }
+
+void Engine::Trial::medians(Transport* tr, uint32_t* dev, double out[2]) {
   std::vector<double> ms[2];
   for (auto& sp : spans) {
-    ms[sp.sched].push_back(be_->timing_ms(sp.a, sp.b));
-    be_->timing_release(sp.a);
-    be_->timing_release(sp.b);
+    ms[sp.kind].push_back(be->timing_ms(sp.a, sp.b));
+    be->timing_release(sp.a);
+    be->timing_release(sp.b);
   }
   spans.clear();
   uint32_t v[2];
@@ -980,12 +926,25 @@ void Engine::trial_medians(std::vector<AutoSpan>& spans, double out[2]) {
     const double med = ms[k].empty() ? 0.0 : ms[k][ms[k].size() / 2];
     v[k] = uint32_t(std::min(4.0e9, std::max(0.0, med * 1e4)));  // 0.1 us units
   }
-  uint32_t* dev = alive_dev_ + 4;
-  be_->copy_h2d(dev, v, sizeof(v));
-  if (tr_->size() > 1) tr_->allreduce_max_u32(dev, 2, be_->stream());
-  be_->copy_d2h(v, dev, sizeof(v));
+  be->copy_h2d(dev, v, sizeof(v));
+  if (tr->size() > 1) tr->allreduce_max_u32(dev, 2, be->stream());
+  be->copy_d2h(v, dev, sizeof(v));
   out[0] = v[0] * 1e-4;
   out[1] = v[1] * 1e-4;
+}
+
+void Engine::Trial::drop_open() {
+  if (open) be->timing_release(open);
+  open = nullptr;
+}
+
+void Engine::Trial::release() {
+  for (auto& sp : spans) {
+    be->timing_release(sp.a);
+    be->timing_release(sp.b);
+  }
+  spans.clear();
+  drop_open();
 }
 
 // Poll placement trial (tuning side_poll = -1).  Once the overlap trial has
@@ -1006,22 +965,13 @@ void Engine::trial_medians(std::vector<AutoSpan>& spans, double out[2]) {
 // the critical path (src/game_mpi_collective.c:70-109).
 void Engine::poll_trial_step() {
   if (auto_overlap_) return;  // the overlap trial runs first
-  if (ptrial_open_) {
-    void* end = be_->timing_mark(nullptr);
-    if (ptrial_mode_ >= 0) {
-      ptrial_spans_.push_back({ptrial_mode_, ptrial_open_, end});
-      ++ptrial_counts_[ptrial_mode_];
-    } else {
-      be_->timing_release(ptrial_open_);
-      be_->timing_release(end);
-    }
-    ptrial_open_ = nullptr;
-  }
-  if (!ptrial_verify_ && ptrial_counts_[0] >= kAutoTrials && ptrial_counts_[1] >= kAutoTrials) {
-    trial_medians(ptrial_spans_, poll_ms_);
+  uint32_t* scratch = alive_dev_ + 4;
+  ptrial_.close();
+  if (!ptrial_verify_ && ptrial_.full(0) && ptrial_.full(1)) {
+    ptrial_.medians(tr_, scratch, poll_ms_);
     if (poll_ms_[1] < 0.98 * poll_ms_[0]) {  // side wins the alternation: check a run of side windows
       ptrial_verify_ = true;
-      ptrial_counts_[0] = ptrial_counts_[1] = 0;
+      ptrial_.counts[0] = ptrial_.counts[1] = 0;
       ptrial_polls_ = 0;
     } else {
       poll_side_ = false;
@@ -1029,9 +979,9 @@ void Engine::poll_trial_step() {
       poll_decided_ = true;
       return;
     }
-  } else if (ptrial_verify_ && ptrial_counts_[1] >= kAutoTrials) {
+  } else if (ptrial_verify_ && ptrial_.full(1)) {
     double v[2];
-    trial_medians(ptrial_spans_, v);
+    ptrial_.medians(tr_, scratch, v);
     poll_side_steady_ms_ = v[1];
     poll_side_ = v[1] < poll_ms_[0];
     poll_trial_ = false;
@@ -1039,12 +989,13 @@ void Engine::poll_trial_step() {
     return;
   }
   const int64_t i = ptrial_polls_++;
+  int mode;  // placement of the window that opens here: 0 joined, 1 side, -1 warm-up
   if (ptrial_verify_)
-    ptrial_mode_ = i < 1 ? -1 : 1;
+    mode = i < 1 ? -1 : 1;
   else
-    ptrial_mode_ = i < kAutoWarm ? -1 : int((i - kAutoWarm) % 2);
-  poll_side_ = ptrial_verify_ || ptrial_mode_ == 1;
-  ptrial_open_ = be_->timing_mark(nullptr);
+    mode = i < kAutoWarm ? -1 : int((i - kAutoWarm) % 2);
+  poll_side_ = ptrial_verify_ || mode == 1;
+  ptrial_.begin(mode);
 }
 
 std::string Engine::poll_mode() const {
@@ -1055,7 +1006,7 @@ std::string Engine::poll_mode() const {
 
 void Engine::auto_decide() {
   // Slowest rank decides: every rank ends up with the same MAX values.
-  trial_medians(auto_spans_, auto_ms_);
+  otrial_.medians(tr_, alive_dev_ + 4, auto_ms_);
   const double v[2] = {auto_ms_[0], auto_ms_[1]};
   bool alt = v[1] < 0.98 * v[0];
   const std::string& forced = cfg_.tune.s("overlap_auto");  // fault injection (tests)
@@ -1091,7 +1042,7 @@ void Engine::collect_phases(RunResult& res) {
   if (!phase_timing_) return;
   double ms[kPhases] = {0, 0, 0, 0};
   for (auto& sp : phase_spans_) {
-    ms[sp.phase] += be_->timing_ms(sp.a, sp.b);
+    ms[sp.kind] += be_->timing_ms(sp.a, sp.b);
     be_->timing_release(sp.a);
     be_->timing_release(sp.b);
   }

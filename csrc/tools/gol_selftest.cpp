@@ -105,6 +105,82 @@ bool run_case(const Case& k) {
   return ok;
 }
 
+// Allocation failures while an engine is built (tuning fault_alloc=N: the CPU
+// backend's N-th allocation throws): N = 1, 2, ... until an engine is built
+// and has run.  A failed attempt must leave nothing allocated - LeakSanitizer
+// (the address build) reports what it does leave - and the attempt that gets
+// through must still compute the oracle's result.
+bool alloc_fault_case(const char* what, Layout layout, int u8_compute, const char* ring, const std::string& decomp,
+                      int P, int min_ctor_faults) {
+  const int64_t W = 64, H = 32, gens = 8;
+  std::vector<uint8_t> grid = random_cells(W, H, 9, 0.4);
+  std::vector<uint8_t> ref = grid;
+  const RefResult rr = cpu_reference_run(ref, W, H, gens, true, 3, 1);
+
+  auto hub = std::make_shared<ThreadHub>(P);
+  std::vector<uint8_t> out(grid.size(), 0);
+  const size_t np = size_t(P);
+  std::vector<int> ctor_faults(np, 0), run_faults(np, 0);
+  std::vector<std::string> errs(np);
+  std::vector<std::thread> ts;
+  for (int r = 0; r < P; ++r) {
+    ts.emplace_back([&, r] {
+      // Every rank makes the same allocations, so all of them fail at the
+      // same N, before their engines first talk to each other.
+      for (int n = 1; n <= 64; ++n) {
+        bool built = false;
+        try {
+          Tuning tune = Tuning::from_env();
+          tune.set("fault_alloc", std::to_string(n)).set("cpu_ring", ring);
+          auto be = make_cpu_backend(2, -1, tune);
+          ThreadTransport tr(hub, r, be.get());
+          EngineConfig cfg;
+          cfg.W = W;
+          cfg.H = H;
+          cfg.layout = layout;
+          cfg.u8_compute = u8_compute;
+          cfg.decomp = decomp;
+          cfg.gen_limit = gens;
+          cfg.poll_gens = 5;
+          cfg.tune = tune;
+          Engine eng(cfg, be.get(), &tr);
+          built = true;
+          if (std::string(ring) == "1" && !eng.row_ring()) fail("no row ring");
+          eng.load_global(grid.data(), W);
+          const RunResult res = eng.run();  // allocates the flags: one more N fails here
+          if (res.generations != rr.generations) fail("generations differ from the oracle");
+          const Extent rows = eng.rows(), cols = eng.cols();
+          std::vector<uint8_t> tile(size_t(rows.size() * cols.size()));
+          eng.store_cells(tile.data(), cols.size(), false);
+          for (int64_t i = 0; i < rows.size(); ++i)
+            for (int64_t j = 0; j < cols.size(); ++j)
+              out[size_t((rows.begin + i) * W + cols.begin + j)] = tile[size_t(i * cols.size() + j)];
+          return;
+        } catch (const std::exception& e) {
+          if (std::string(e.what()).find("allocation of") == std::string::npos) {
+            errs[size_t(r)] = e.what();
+            return;
+          }
+          ++(built ? run_faults : ctor_faults)[size_t(r)];
+        }
+      }
+      errs[size_t(r)] = "no attempt got through";
+    });
+  }
+  for (auto& t : ts) t.join();
+  bool ok = out == ref;
+  for (int r = 0; r < P; ++r) {
+    if (!errs[size_t(r)].empty()) {
+      std::printf("  rank %d error: %s\n", r, errs[size_t(r)].c_str());
+      ok = false;
+    }
+    if (ctor_faults[size_t(r)] < min_ctor_faults || ctor_faults[size_t(r)] != ctor_faults[0]) ok = false;
+  }
+  std::printf("alloc faults %-22s %s P=%d: %d constructions and %d runs failed, then 8 generations -> %s\n", what,
+              decomp.c_str(), P, ctor_faults[0], run_faults[0], ok ? "ok" : "MISMATCH");
+  return ok;
+}
+
 bool text_roundtrip() {
   const int64_t W = 77, H = 31;
   std::vector<uint8_t> g = random_cells(W, H, 5, 0.4);
@@ -197,6 +273,10 @@ int main() {
   };
   bool ok = unit_checks();
   for (const Case& k : cases) ok = run_case(k) && ok;
+  // Ring, byte and bit buffers live (2 byte tiles + the alive word before the
+  // engine stands); column buffers live (4 more).
+  ok = alloc_fault_case("u8 on bit rings", Layout::U8, 1, "1", "1x1", 1, 3) && ok;
+  ok = alloc_fault_case("bits, column halos", Layout::Bits, -1, "0", "2x2", 4, 7) && ok;
   ok = text_roundtrip() && ok;
   std::printf(ok ? "SELFTEST OK\n" : "SELFTEST FAILED\n");
   return ok ? 0 : 1;

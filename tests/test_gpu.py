@@ -691,7 +691,7 @@ def test_linked_launches_termination_and_subdomains(gpu, tune):
     assert (grp.gather() == want).all()
 
 
-# ---- byte layout on bit words (Engine::epoch_via_bits), the GPU default ----
+# ---- byte layout on bit words (Engine::run_epoch on the bit image), the GPU default ----
 
 @pytest.mark.parametrize("W,H,gens,tmax", [(32, 1, 40, 0), (96, 70, 77, 4), (2048, 40, 200, 0), (6400, 700, 131, 8),
                                            (8192, 1024, 1000, 0)])

@@ -1,5 +1,5 @@
 """Byte layout computed on bit words (EngineConfig::u8_compute = bits,
-Engine::epoch_via_bits): the byte-per-cell grid stays the storage, each epoch
+Engine::run_epoch on the bit image): the byte-per-cell grid stays the storage, each epoch
 packs its owned rows into bit words in the spare byte buffer, exchanges or
 fills the halos there and runs the bit-layout temporal blocks, then unpacks.
 On the CPU backend (default: bytes) it is selected explicitly; every result is
