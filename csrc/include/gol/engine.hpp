@@ -176,10 +176,22 @@ class Engine {
   bool phase_timing() const { return phase_timing_; }
   bool graphs() const { return use_graphs_; }
   int64_t generation() const { return gen_; }
-  void set_generation(int64_t g) { gen_ = g; }
+  void set_generation(int64_t g) {
+    replay_tail();
+    gen_ = g;
+  }
+  // Lazy tail (tuning lazy_tail; run_impl): the generation the block chain
+  // has reached - generation(), or up to tmax() - 1 generations past it after
+  // a run that ended on a full block instead of a remainder - and how many
+  // runs ended that way / how many of those blocks a read of the grid had to
+  // rewind and replay as remainder blocks (replay_tail).
+  int64_t spine_generation() const { return gen_ + ahead_; }
+  int64_t tail_overshoots() const { return tail_overshoots_; }
+  int64_t tail_replays() const { return tail_replays_; }
   Backend* backend() const { return be_; }
   // The byte (or bit) tile's current buffer, brought up to date first.
   void* current_buffer() {
+    replay_tail();
     sync_bytes();
     be_->quiet_invalidate();  // the caller may write through the pointer
     return buf_[cur_];
@@ -431,6 +443,23 @@ class Engine {
   quiet::Policy quiet_;
   int64_t quiet_seq_seen_ = 0, quiet_skipped_tiles_ = 0;
   void quiet_poll();
+  // Lazy tail (tuning lazy_tail).  ahead_ > 0: the compute tile's current
+  // buffer holds generation gen_ + ahead_ (the spine), the other one still
+  // holds the last block's input, generation gen_ + ahead_ - tmax_, and the
+  // flags of (gen_, gen_ + ahead_] wait on the device for the next run.
+  bool tail_ok_ = false;       // the tile may end a run on a full block (single-rank ring, D = tmax, no graphs)
+  int tail_mode_ = 0;          // tuning lazy_tail
+  int64_t ahead_ = 0;
+  int64_t tail_drift_ = 0;     // drift_ before that block
+  bool tail_hold_ = false;     // auto: the last such block was replayed for a read; remainder blocks until
+  bool grid_read_ = false;     // ... a run follows a run with no read of the grid in between
+  bool no_flags_ = false;      // launches of a replay record no flags
+  int64_t tail_overshoots_ = 0, tail_replays_ = 0;
+  Owned<uint32_t> carry_;      // device: the carried flags between a run's flag reset and their new offsets
+  bool tail_wanted();
+  // Brings the grid to generation gen_ when the block chain is ahead of it;
+  // everything that reads or writes the grid outside a run calls it first.
+  void replay_tail();
   // Overlap auto trial.
   bool auto_overlap_ = false;       // trial still running
   bool auto_decided_ = false;

@@ -322,6 +322,9 @@ PYBIND11_MODULE(_gol, m) {
       .def_property_readonly("quiet_blocks_skip", &Engine::quiet_blocks_skip)
       .def_property_readonly("quiet_waves_launched", &Engine::quiet_waves_launched)
       .def_property_readonly("quiet_waves_skipped", &Engine::quiet_waves_skipped)
+      .def_property_readonly("spine_generation", &Engine::spine_generation)
+      .def_property_readonly("tail_overshoots", &Engine::tail_overshoots)
+      .def_property_readonly("tail_replays", &Engine::tail_replays)
       .def_property("phase_timing", &Engine::phase_timing, &Engine::set_phase_timing)
       .def("graphs", &Engine::graphs)
       .def_property("generation", &Engine::generation, &Engine::set_generation)

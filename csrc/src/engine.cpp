@@ -230,6 +230,10 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
     quiet_.off = qt.off;
     be_->quiet_prepare(compute_geom());
   }
+  // Lazy tail (run_impl): single-rank ring tiles whose epochs are one block.
+  tail_mode_ = cfg_.tune.i("lazy_tail");
+  tail_ok_ = tail_mode_ != 0 && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
+  if (tail_ok_) carry_ = Owned<uint32_t>(be_, be_->alloc(size_t(tmax_) * 4));
   gen_ = cfg_.start_gen;
 }
 
@@ -253,6 +257,7 @@ Engine::~Engine() {
 
 void Engine::load_cells(const uint8_t* cells, int64_t ld) {
   settle_pending(true);
+  ahead_ = 0;          // a block chain ahead of gen_ goes with the old state
   bits_live_ = false;  // the byte tile is the state again
   be_->load_owned(buf_[cur_], g_, cells, ld);
   be_->synchronize();
@@ -266,6 +271,7 @@ void Engine::load_global(const uint8_t* grid, int64_t ld) {
 
 void Engine::store_cells(uint8_t* cells, int64_t ld, bool ascii) {
   settle_pending(false);
+  replay_tail();
   sync_bytes();
   normalize();
   be_->synchronize();
@@ -276,6 +282,7 @@ void Engine::store_rows(uint8_t* cells, int64_t ld, int64_t r0, int64_t n, bool 
   GOL_REQUIRE(r0 >= 0 && n >= 0 && r0 + n <= g_.H, "store_rows: rows outside the tile");
   if (n == 0) return;
   settle_pending(false);
+  replay_tail();
   sync_bytes();
   normalize();
   be_->synchronize();
@@ -287,6 +294,7 @@ void Engine::store_rows(uint8_t* cells, int64_t ld, int64_t r0, int64_t n, bool 
 
 void Engine::init_random(uint64_t seed, double density) {
   settle_pending(true);
+  ahead_ = 0;
   bits_live_ = false;
   be_->init_random(buf_[cur_], g_, seed, density, rows().begin, cols().begin);
   be_->synchronize();
@@ -296,6 +304,7 @@ void Engine::init_random(uint64_t seed, double density) {
 void Engine::add_drift(int64_t cells) { drift_ = (drift_ + cells) % cfg_.W; }
 
 void Engine::normalize() {
+  replay_tail();
   sync_bytes();  // the rotation's target is the spare byte buffer, which holds the bit image
   if (drift_ == 0) return;
   settle_pending(true);  // the rotated copy has no halo rows
@@ -305,6 +314,7 @@ void Engine::normalize() {
 }
 
 int64_t Engine::alive_count() {
+  replay_tail();
   be_->synchronize();
   const Tile s = state_tile();
   return be_->alive_count(s.cur(), s.g);
@@ -357,7 +367,10 @@ void Engine::exchange_columns(void* buf, const TileGeom& g) {
 // cells travel with the rows): 4 messages instead of the reference's 8
 // per-generation messages with a strided MPI_Type_vector column
 // (src/game_mpi.c:335-383).
-void Engine::halo_exchange() { halo_exchange_on(buf_[cur_], g_); }
+void Engine::halo_exchange() {
+  replay_tail();
+  halo_exchange_on(buf_[cur_], g_);
+}
 
 void Engine::halo_exchange_on(void* buf, const TileGeom& g) {
   trace::Range tr("gol.halo_exchange");
@@ -422,6 +435,7 @@ void* Engine::bit_scratch(int i) const {
 // A drifting bit kernel leaves the byte grid drifted by the same amount (a
 // relabeling of columns, rotated out by normalize() like the bit layout's).
 void Engine::sync_bytes() {
+  replay_tail();  // the image at gen_, not at the spine
   if (!bits_live_) return;
   unpack_bits();
   bits_live_ = false;
@@ -480,6 +494,52 @@ void Engine::settle_pending(bool invalidate) {
   if (!rows_pending_) return;
   be_->synchronize();
   if (invalidate) rows_pending_ = false;
+}
+
+// ---- lazy tail (tuning lazy_tail) -------------------------------------------
+// A run whose last epoch is shorter than a block would finish on remainder
+// blocks (pick_T: 1000 = 83 x 12 + 4): dense launches, after which the next
+// run's first skipping block has no tile words to skip on and recomputes every
+// tile.  Instead run_impl runs one ordinary full block there and reports its
+// limit: gen_ = limit, while the block chain (the spine, gen_ + ahead_) is up
+// to tmax - 1 generations further.  Nothing is lost: the block read one buffer
+// and wrote the other, so its input - generation spine - tmax - is still
+// there (on a row ring the halo rows are mappings of the owned rows), and the
+// flags of (limit, spine] are on the device.
+//   * The next run moves those flags to their new offsets (run_impl), advances
+//     gen_ to min(limit, spine) with no launch and continues from the spine; a
+//     stop inside the carried generations is found by its polls as any other.
+//   * Anything that needs the grid at gen_ first rewinds to the block's input
+//     and runs the remainder blocks after all (replay_tail), as a run without
+//     lazy tails would have.
+// Whether a run ends this way: tail_wanted().
+bool Engine::tail_wanted() {
+  if (!tail_ok_) return false;
+  if (tail_mode_ > 0) return true;
+  // Auto: where the full block is a skipping launch (about a quarter of the
+  // remainder blocks' time on a settled grid, and it keeps the tile words
+  // alive), unless the last one had to be replayed and the grid has been read
+  // after every run since: such a caller would pay a wasted block per run.
+  if (tail_hold_ || quiet_.mode == 0) return false;
+  quiet_poll();
+  return quiet_.mode > 0 || quiet_.skipping;
+}
+
+void Engine::replay_tail() {
+  grid_read_ = true;
+  if (ahead_ == 0) return;
+  trace::Range tr("gol.replay_tail");
+  const int64_t target = gen_;
+  const Tile t = compute_tile();
+  t.par ^= 1;  // the block's input is current again
+  drift_ = tail_drift_;
+  gen_ = target + ahead_ - tmax_;
+  ahead_ = 0;
+  no_flags_ = true;  // the run that reported these generations has their flags
+  run_epoch(target - gen_);
+  no_flags_ = false;
+  ++tail_replays_;
+  tail_hold_ = true;
 }
 
 // Trigger schedule (overlap = 3; Py > 1 or the one-rank RCCL rehearsal, Px
@@ -548,8 +608,9 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
     a.gen_dev = gen_dev_;
     a.gen_rel = gen_base - epoch_start_ + 1;
   } else {
-    a.changed =
-        (flags_ && gen_base + T < flags_base_ + flags_len_ && gen_base >= flags_base_) ? flags_.get() : nullptr;
+    a.changed = (flags_ && !no_flags_ && gen_base + T < flags_base_ + flags_len_ && gen_base >= flags_base_)
+                    ? flags_.get()
+                    : nullptr;
   }
   a.flags_base = flags_base_;
   a.allow_drift = drift_ok_;
@@ -606,6 +667,7 @@ int64_t Engine::quiet_waves_skipped() {
 
 void Engine::step_block(int T, int64_t row_lo, int64_t row_hi) {
   GOL_REQUIRE(!via_bits_, "step_block: the byte tile has no halos when it computes on bit words (u8_compute)");
+  replay_tail();
   add_drift(launch(buf_[cur_], buf_[cur_ ^ 1], g_, T, row_lo, row_hi, gen_));
   cur_ ^= 1;
   gen_ += T;
@@ -735,9 +797,23 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   RunResult res;
   const int64_t start = gen_;
   if (limit < start) limit = start;
-  // (Re)allocate per-generation flags for (start, limit].
-  const int64_t need = limit - start + 2;
+  // Lazy tail, auto: a caller that read the grid after a replayed block and
+  // after every run since keeps the remainder blocks.
+  if (!grid_read_) tail_hold_ = false;
+  grid_read_ = false;
+  // (Re)allocate per-generation flags for (start, limit], and for the full
+  // block a lazy tail may end the run on.
+  const int64_t need = limit - start + 2 + (tail_ok_ ? tmax_ : 0);
+  // The flags of the generations the block chain is ahead, (start, start +
+  // ahead_], were recorded at the last run's offsets: staged through carry_
+  // around the reset, stream-ordered (no host round trip between two runs).
+  const int64_t carried = ahead_;
+  if (carried > 0) {
+    be_->join_streams();
+    be_->copy_2d_async(carry_, carried * 4, flags_ + flag_offset(start), carried * 4, carried * 4, 1);
+  }
   if (!flags_ || flags_len_ < need) {
+    if (carried > 0) be_->synchronize();  // the copy reads the buffer that goes
     flags_.reset();
     flags_host_.reset();
     flags_len_ = std::max<int64_t>(need, 64);
@@ -746,6 +822,8 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   }
   flags_base_ = start;
   be_->memset_async(flags_, 0, size_t(flags_len_) * 4);
+  if (carried > 0)
+    be_->copy_2d_async(flags_ + flag_offset(start), carried * 4, carry_.get(), carried * 4, carried * 4, 1);
   if (use_graphs_) {
     if (graph_flags_ != flags_) release_graphs();  // kernel arguments point at the flags
     graph_flags_ = flags_;
@@ -774,7 +852,22 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   while (gen_ < limit) {
     const int64_t d = std::min<int64_t>(D_, limit - gen_);
     send_next_ = gen_ + d < limit;
-    if (use_graphs_ && d == D_) {
+    if (ahead_ > 0) {
+      // Generations the block chain has reached already (lazy tail): no
+      // launch; their flags are in the window, polled like any others.
+      const int64_t k = std::min(ahead_, limit - gen_);
+      gen_ += k;
+      ahead_ -= k;
+    } else if (d < D_ && tail_wanted()) {
+      // Lazy tail: one full block from the spine instead of the remainder
+      // blocks; the generations beyond the limit belong to the next run.
+      GOL_REQUIRE(gen_ + tmax_ < flags_base_ + flags_len_, "lazy tail: flag window too short");
+      tail_drift_ = drift_;
+      run_epoch(D_);
+      ahead_ = gen_ - limit;
+      gen_ = limit;
+      ++tail_overshoots_;
+    } else if (use_graphs_ && d == D_) {
       // Full epochs replay a captured graph; the only per-epoch input is the
       // device generation offset, advanced by the graph itself.  Graphs are
       // keyed by the parity of the buffer pair the epochs alternate over and

@@ -41,6 +41,11 @@ const std::vector<TuningKey>& tuning_keys() {
       {"quiet_off", "GOL_QUIET_OFF", "35", 'i', "tune", "quiet_skip auto: percent of clean tiles below which it stops"},
       {"quiet_rows", "GOL_QUIET_ROWS", "96", 'i', "tune",
        "output rows per 4-wave group (one tile) of the skipping kernel's plan"},
+      {"lazy_tail", "GOL_LAZY_TAIL", "-1", 'i', "tune",
+       "a run whose last epoch is shorter than a block runs one full block instead and reports its limit; the "
+       "generations beyond it carry into the next run, and a read of the grid rewinds and replays the remainder "
+       "(single-rank ring tiles, one block per epoch, no graphs): -1 where that block would run the skipping kernel "
+       "(and not right after a replayed one), 0 never (remainder blocks), 1 always"},
       {"u8_kernel", "GOL_U8_KERNEL", "auto", 's', "tune", "byte kernel on the bytes themselves: auto | lds"},
       {"lds_rows", "GOL_LDS_ROWS", "32", 'i', "tune", "rows per LDS tile of the byte LDS kernel"},
       {"lds_t", "GOL_LDS_T", "0", 'i', "tune", "generations per LDS pass (0: 32 packed, 8 unpacked)"},

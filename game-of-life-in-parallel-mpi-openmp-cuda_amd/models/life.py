@@ -146,7 +146,7 @@ def make_backend(engine: str = "auto", device: int = 0, threads: int = 0, tune=N
 # Tuning keys the engine reads from EngineConfig::tune (engine.cpp); the rest
 # are read by the backend (or the transports) at construction.
 _ENGINE_KEYS = frozenset({"u8_via_bits", "side_poll", "poll_copy_side", "watchdog_s", "overlap_auto",
-                          "cpu_side_poll"})
+                          "cpu_side_poll", "lazy_tail"})
 
 
 @dataclasses.dataclass
@@ -265,6 +265,12 @@ class Simulation:
                                  "skip": self._eng.quiet_blocks_skip},
                 "quiet_waves_launched": self._eng.quiet_waves_launched,
                 "quiet_waves_skipped": self._eng.quiet_waves_skipped,
+                # Lazy tail (tuning lazy_tail): the generation the block chain has reached (up to
+                # tmax - 1 past `generation` after a run that ended on a full block), runs that
+                # ended that way, and how many of those blocks a read of the grid had to replay.
+                "spine_generation": self._eng.spine_generation,
+                "tail_overshoots": self._eng.tail_overshoots,
+                "tail_replays": self._eng.tail_replays,
                 "launch_paths": dict(self.backend.launch_paths()),
                 "tuning": self.tuning(), "tuning_changed": self.tuning_changed()}
 
