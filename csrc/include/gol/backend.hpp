@@ -184,6 +184,12 @@ class Backend {
   // Waves per tile of the skipping kernel, and tiles launched by it so far.
   virtual int quiet_tile_waves() const { return 0; }
   virtual int64_t quiet_tiles_launched() const { return 0; }
+  // The candidate list (tuning quiet_list): whether skipping blocks launch
+  // only the tiles next to the last block's activity, and how many tiles the
+  // newest finished launch listed for its successor (-1: none reported).
+  // Tiles that are not launched count as launched, clean and skipped above.
+  virtual bool quiet_list() const { return false; }
+  virtual int64_t quiet_candidates() const { return -1; }
   // Whether run_block evaluates `rule` (BlockArgs::rule) on tiles of this
   // layout.  The CPU backend runs any rule without B0; the HIP backend the
   // rules compiled from csrc/kernels/life_rules.def.  unsupported_rule() is

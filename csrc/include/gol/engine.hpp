@@ -207,6 +207,8 @@ class Engine {
   int64_t quiet_blocks_skip() const { return quiet_.blocks_skip; }
   int64_t quiet_waves_launched() const { return be_->quiet_tiles_launched() * be_->quiet_tile_waves(); }
   int64_t quiet_waves_skipped();
+  bool quiet_list() const { return quiet_.mode != 0 && be_->quiet_list(); }
+  int64_t quiet_candidates() const { return be_->quiet_candidates(); }
   // Storage-frame drift (cells, mod W) left by drifting kernels
   // (Backend::drifts): stored column x holds true column x - drift.
   int64_t drift() const { return drift_; }

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define GOL_HD __host__ __device__
@@ -44,6 +45,53 @@ GOL_HD inline bool may_skip(const uint32_t* nb) {
   if (both(nb[0], kBot, kRight) || both(nb[2], kBot, kLeft)) return false;
   if (both(nb[6], kTop, kRight) || both(nb[8], kTop, kLeft)) return false;
   return true;
+}
+
+// ---- The candidate list (tuning quiet_list) ----
+// A tile's skip test reads the nine words of its 3 x 3 neighbourhood.  A
+// skipped tile republishes its word unchanged, so if no tile of that
+// neighbourhood computed in block n, the nine words - and with them the
+// decision, the rows and the tile's own word in both maps - are in block n + 1
+// what they were in block n: only the neighbours of the tiles that computed
+// need a launch - and of those only the neighbours of tiles whose word
+// changed: a tile that computed and published the word it had published before
+// (an oscillator or a glider inside a tile) leaves the tiles around it the
+// inputs they had.  A tile that computed is launched in the next block in any
+// case, where it writes the other map.
+GOL_HD inline bool marks_neighbours(uint32_t old_word, uint32_t new_word) { return old_word != new_word; }
+
+// Tile i (0..8, row-major as may_skip's nb[]) of the neighbourhood of tile
+// (strip kcol, group grp) on the torus of ncolw x nseg tiles.  The relation is
+// symmetric: the tiles that read a tile's word are its neighbourhood.
+GOL_HD inline int neighbour(int kcol, int grp, int i, int ncolw, int nseg) {
+  const int g = (grp + i / 3 - 1 + nseg) % nseg;
+  const int k = (kcol + i % 3 - 1 + ncolw) % ncolw;
+  return k * nseg + g;
+}
+
+// Change flags of the tiles that are not launched: per level, how many tiles'
+// current word has the level's flag, kFlagsPerWord levels of kFlagBits bits
+// to a 64-bit counter word (fewer than 2^20 tiles).  A computing tile adds the
+// difference between its new and its old word; the borrows of a negative
+// field cancel in the sum, which is the count of a set of tiles.
+constexpr int kFlagBits = 21, kFlagsPerWord = 3;
+constexpr int flag_words(int T) { return (T + kFlagsPerWord - 1) / kFlagsPerWord; }
+GOL_HD inline unsigned long long flag_delta(uint32_t old_word, uint32_t new_word, int w) {
+  unsigned long long d = 0;
+  for (int j = 0; j < kFlagsPerWord; ++j) {
+    const int L = w * kFlagsPerWord + j;
+    if (L >= 16) break;
+    const long long dl = (long long)((new_word >> L) & 1u) - (long long)((old_word >> L) & 1u);
+    d += (unsigned long long)dl << (kFlagBits * j);
+  }
+  return d;
+}
+// The levels whose count in counter word w is not zero, as flag bits.
+GOL_HD inline uint32_t flag_levels(unsigned long long count, int w) {
+  uint32_t m = 0;
+  for (int j = 0; j < kFlagsPerWord; ++j)
+    if ((count >> (kFlagBits * j)) & ((1ull << kFlagBits) - 1)) m |= 1u << (w * kFlagsPerWord + j);
+  return m & kFlagMask;
 }
 
 // What identifies the words a block published: a later block may read them
@@ -116,6 +164,87 @@ struct Policy {
     return mode == 0 ? "off" : mode > 0 ? "on" : skipping ? "auto:skipping" : "auto:dense";
   }
 };
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// Host model of the skipping kernel's candidate list, one call per block, as
+// the kernel keeps it: two word maps, the launch stamps that de-duplicate the
+// marks, the flag counts.  `fresh[t]` is the word tile t publishes if it
+// computes in this block; `follow` false is a launch with no words to read
+// (every tile computes, the next block evaluates every tile).
+class ListModel {
+ public:
+  ListModel(int ncolw, int nseg, int T)
+      : ncolw_(ncolw), nseg_(nseg), T_(T), stamp_(size_t(ncolw) * nseg, 0u), counts_(size_t(flag_words(T)), 0ull) {
+    map_[0].assign(stamp_.size(), 0u);
+    map_[1].assign(stamp_.size(), 0u);
+  }
+  // Runs one block; returns the tiles that computed, in launch order.
+  std::vector<int> block(const std::vector<uint32_t>& fresh, bool follow) {
+    const int tiles = int(stamp_.size());
+    ++seq_;
+    const std::vector<uint32_t>& prev = map_[cur_];
+    std::vector<uint32_t>& next = map_[cur_ ^ 1];
+    std::vector<int> items, marked, computed;
+    if (!follow || all_) {
+      for (int t = 0; t < tiles; ++t) items.push_back(t);
+    } else {
+      items = list_;
+    }
+    if (!follow) counts_.assign(counts_.size(), 0ull);
+    launched_ = int64_t(items.size());
+    for (int t : items) {
+      const int kcol = t / nseg_, grp = t % nseg_;
+      uint32_t nb[9];
+      for (int i = 0; i < 9; ++i) nb[i] = prev[size_t(neighbour(kcol, grp, i, ncolw_, nseg_))];
+      if (follow && may_skip(nb)) {
+        next[size_t(t)] = nb[4];
+        continue;
+      }
+      next[size_t(t)] = fresh[size_t(t)];
+      computed.push_back(t);
+      for (size_t w = 0; w < counts_.size(); ++w) counts_[w] += flag_delta(follow ? nb[4] : 0u, fresh[size_t(t)], int(w));
+      if (!follow) continue;
+      for (int i = 0; i < 9; ++i) {
+        if (i != 4 && !marks_neighbours(nb[4], fresh[size_t(t)])) continue;
+        const int n = neighbour(kcol, grp, i, ncolw_, nseg_);
+        if (stamp_[size_t(n)] != seq_) {
+          stamp_[size_t(n)] = seq_;
+          marked.push_back(n);
+        }
+      }
+    }
+    list_ = marked;
+    all_ = !follow;
+    cur_ ^= 1;
+    return computed;
+  }
+  const std::vector<uint32_t>& words() const { return map_[cur_]; }       // the map the last block wrote
+  const std::vector<uint32_t>& words_before() const { return map_[cur_ ^ 1]; }
+  int64_t launched() const { return launched_; }                          // tiles the last block launched
+  int64_t candidates() const { return all_ ? int64_t(stamp_.size()) : int64_t(list_.size()); }  // of the next block
+  // Levels some tile's current word flags (what the kernel ORs into changed[]).
+  uint32_t flags() const {
+    uint32_t m = 0;
+    for (size_t w = 0; w < counts_.size(); ++w) m |= flag_levels(counts_[w], int(w));
+    return m & ((1u << T_) - 1u);
+  }
+  std::vector<int64_t> flag_counts() const {
+    std::vector<int64_t> c(size_t(T_), 0);
+    for (int L = 0; L < T_; ++L)
+      c[size_t(L)] = int64_t((counts_[size_t(L / kFlagsPerWord)] >> (kFlagBits * (L % kFlagsPerWord))) & ((1ull << kFlagBits) - 1));
+    return c;
+  }
+
+ private:
+  int ncolw_, nseg_, T_, cur_ = 0;
+  uint32_t seq_ = 0;
+  bool all_ = true;
+  int64_t launched_ = 0;
+  std::vector<uint32_t> map_[2], stamp_;
+  std::vector<int> list_;
+  std::vector<unsigned long long> counts_;
+};
+#endif  // !__HIP_DEVICE_COMPILE__
 
 }  // namespace quiet
 }  // namespace gol

@@ -13,7 +13,7 @@ using QuietIO = lb::BitsIO<1, kXlaneDpp>;
 // Up front, outside any timed run: the maps and counters of a tile of H rows
 // and `words` owned words per row, whatever the plan, and the kernel's code
 // object loaded (a first launch otherwise loads it).
-void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words) {
+void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words, bool list) {
   const int64_t min_rows = int64_t(kQuietM - 1) * 2 * kQuietT + 1;
   const int64_t tiles = ceil_div(words, int64_t(lb::wave_out_words<kXlaneDpp, 1>())) * std::max<int64_t>(1, H / min_rows);
   if (tiles >= (int64_t(1) << 20)) return;
@@ -21,7 +21,14 @@ void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words) {
   scratch.get(Scratch::kQuietMapB, size_t(tiles) * 4);
   scratch.get(Scratch::kQuietCounters, kQuietCountBytes);
   hipFuncAttributes attr;
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM>));
+  if (list) {
+    scratch.get(Scratch::kQuietList, QuietListLayout(tiles).bytes);
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, true, false>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, true, true>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_chunk_kernel<kQuietT, QuietIO>));
+  } else {
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, false>));
+  }
   (void)hipGetLastError();
 }
 
@@ -50,10 +57,70 @@ int64_t launch_bits_w1_dpp_quiet(const LifeBlockParams& p0, int64_t out_rows, in
   p.quiet_count = reinterpret_cast<unsigned long long*>(ctx.scratch->get(Scratch::kQuietCounters, kQuietCountBytes));
   p.quiet_report = ctx.mail->quiet_report;
   p.quiet_seq = ++Q->seq;
-  hipLaunchKernelGGL((lb::life_quiet_kernel<kQuietT, IO, M>), dim3(unsigned(tiles)), dim3(64 * M), 0, s, p);
+  int64_t grid = tiles;
+  if (Q->list) {
+    // The candidate list: this launch's items are what the last launch
+    // appended, if it followed a launch itself (else it computed every tile,
+    // and every tile is evaluated now, which
+    // counts the flags from zero, in the set the last launch zeroed).
+    const QuietListLayout lay(tiles);
+    uint8_t* const base = reinterpret_cast<uint8_t*>(ctx.scratch->get(Scratch::kQuietList, lay.bytes));
+    const bool listed = p.quiet_prev && Q->listed;
+    const int items_next = Q->items ^ 1;
+    p.quiet_lc = reinterpret_cast<unsigned long long*>(base);
+    p.quiet_stamp = reinterpret_cast<uint32_t*>(base + lay.stamp);
+    p.quiet_items = listed ? reinterpret_cast<const uint32_t*>(base + lay.items[Q->items]) : nullptr;
+    p.quiet_items_next = reinterpret_cast<uint32_t*>(base + lay.items[items_next]);
+    p.quiet_cap = lay.cap;
+    p.quiet_acc = reinterpret_cast<unsigned long long*>(base + lay.acc);
+    if (p.quiet_prev && !listed) Q->fset ^= 1;
+    p.quiet_fset = Q->fset;
+    // What the newest finished launch reported for its successor (the host
+    // does not know this launch's list length): valid if that launch listed.
+    int64_t reported = -1;
+    if (listed && ctx.mail_host) {
+      const unsigned long long r = __atomic_load_n(&ctx.mail_host->quiet_report[2], __ATOMIC_ACQUIRE);
+      int64_t n = int64_t((Q->seq - 1) & ~0xFFFFFFu) | int64_t(r >> 40);
+      if (n > int64_t(Q->seq - 1)) n -= int64_t(1) << 24;
+      if (r != 0 && Q->listed_since != 0 && n >= int64_t(Q->listed_since)) reported = int64_t(r & 0xFFFFFu);
+    }
+    const int64_t sized = reported >= 0 ? std::min<int64_t>(tiles, 2 * reported + 256) : tiles;
+    // Short waves where the list is short: K one-wave workgroups per item,
+    // forced (quiet_chunks = n: every list launch) or, by default, when K
+    // times the reported length fits quiet_chunk_waves (-n: with K = n).  The
+    // report lags, so twice that length and 256 items' worth of waves are
+    // launched; the kernel strides over its units, whatever its grid.
+    int K = 1;
+    const int k_auto = Q->chunks < -1 ? -Q->chunks : kQuietChunksAuto;
+    if (Q->chunks > 1) K = Q->chunks;
+    else if (Q->chunks < 0 && reported >= 0 && reported * k_auto <= Q->chunk_waves) K = k_auto;
+    K = std::max(1, std::min<int>(K, std::min<int>(kQuietChunksMax, p.seg_rows)));
+    Q->chunks_last = K;
+    // The grouped kernel's grid: by default one group per tile of the plan,
+    // which covers any list - the groups beyond it return on their first load,
+    // and the kernel needs no loop.  quiet_grid > 0 forces a grid, -1 takes
+    // the size above; both run the looping kernel, right with any grid.
+    if (K > 1) {
+      p.quiet_chunks = K;
+      grid = (Q->grid > 0 ? std::min<int64_t>(Q->grid, tiles) : sized) * K;
+      hipLaunchKernelGGL((lb::life_quiet_chunk_kernel<kQuietT, IO>), dim3(unsigned(grid)), dim3(64), 0, s, p);
+    } else if (Q->grid != 0) {
+      grid = Q->grid > 0 ? std::min<int64_t>(Q->grid, tiles) : sized;
+      hipLaunchKernelGGL((lb::life_quiet_kernel<kQuietT, IO, M, true, true>), dim3(unsigned(grid)), dim3(64 * M), 0, s, p);
+    } else {
+      hipLaunchKernelGGL((lb::life_quiet_kernel<kQuietT, IO, M, true, false>), dim3(unsigned(grid)), dim3(64 * M), 0, s, p);
+    }
+    Q->listed = p.quiet_prev != nullptr;
+    if (!Q->listed) Q->listed_since = 0;
+    else if (Q->listed_since == 0) Q->listed_since = Q->seq;
+    Q->items = items_next;
+  } else {
+    hipLaunchKernelGGL((lb::life_quiet_kernel<kQuietT, IO, M, false>), dim3(unsigned(tiles)), dim3(64 * M), 0, s, p);
+  }
   Q->prev = cur;
   Q->cur = next;
   Q->tiles = tiles;
+  Q->grid_last = grid;
   return tiles;
 }
 

@@ -104,6 +104,26 @@ struct LifeBlockParams {
   unsigned long long* quiet_count;
   unsigned long long* quiet_report;
   uint32_t quiet_seq;
+  // The candidate list (life_quiet_kernel<..., LIST = true>; gol/quiet.hpp):
+  // the launch runs the tiles of quiet_items - kQuietCounters inclusive
+  // sub-list ends, then the sub-lists of quiet_cap entries each; null: every
+  // tile - as item blockIdx.x (the looping kernel: further items from a
+  // ticket, whatever its grid), and its computing tiles append the next
+  // block's candidates to quiet_items_next, de-duplicated by
+  // quiet_stamp[tile] == quiet_seq.  quiet_lc: the 64-bit words of
+  // QuietListWords; quiet_fset: the flag-count set it updates.
+  // quiet_report[2]: quiet_seq << 40 | the next block's candidates.
+  const uint32_t* quiet_items;
+  uint32_t* quiet_items_next;
+  uint32_t* quiet_stamp;
+  unsigned long long* quiet_lc;
+  int quiet_cap;
+  int quiet_fset;
+  // Short waves (life_quiet_chunk_kernel): one-wave workgroups per item, and
+  // the 64-bit word-and-arrival accumulator of every tile (zero between
+  // launches).
+  int quiet_chunks;
+  unsigned long long* quiet_acc;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -197,13 +217,24 @@ struct QuietState {
   uint32_t seq = 0;                // launches so far (24 bits reach the report)
   int64_t tiles = 0;               // tiles of the last launch
   int seg_rows = 96;               // output rows per group the plan aims at (tuning quiet_rows)
+  // The candidate list (tuning quiet_list, quiet_grid).
+  bool list = false;               // launches run the list kernel
+  int grid = 0;                    // grid of a list launch: 0 every tile, n forced, -1 from the newest report
+  bool listed = false;             // the last launch appended the next block's candidates
+  uint32_t listed_since = 0;       // first launch of the unbroken run of appending launches (0: none)
+  int items = 0;                   // item buffer the last launch appended to
+  int fset = 0;                    // flag-count set the last launch updated
+  int64_t grid_last = 0;           // groups of the last launch
+  int chunks = -1;                 // tuning quiet_chunks: -1 by the reported list length, 1 off, n forced
+  int64_t chunk_waves = 1024;      // tuning quiet_chunk_waves: most one-wave workgroups an automatic choice makes
+  int chunks_last = 1;             // one-wave workgroups per item of the last launch (1: the grouped kernel)
 };
 
 // Words the kernels write for the host: one fine-grained pinned host
 // allocation, written through its device alias and read without a copy.
 struct Mailbox {
   uint32_t err[4];  // LifeBlockParams::err: the code (check_device_errors), then a give-up's diagnostics
-  unsigned long long quiet_report[2];  // LifeBlockParams::quiet_report
+  unsigned long long quiet_report[3];  // LifeBlockParams::quiet_report
 };
 
 // Device memory that persists across launches, owned by the backend: one
@@ -212,7 +243,10 @@ struct Mailbox {
 // a fill on the compute stream, which orders it before the launch it is for.
 class Scratch {
  public:
-  enum Slot { kChainFlags, kChainSlots, kLinkWordsA, kLinkWordsB, kLinkWordsC, kQuietMapA, kQuietMapB, kQuietCounters, kSlots };
+  enum Slot {
+    kChainFlags, kChainSlots, kLinkWordsA, kLinkWordsB, kLinkWordsC, kQuietMapA, kQuietMapB, kQuietCounters,
+    kQuietList, kSlots
+  };
   static constexpr Slot kLinkWords[3] = {kLinkWordsA, kLinkWordsB, kLinkWordsC};  // LinkState::flags
   // The two compute streams (the second may be null), which both drain before
   // a buffer is replaced; check_dev >= 0: every buffer handed out is checked
@@ -262,6 +296,7 @@ struct LifeTuning {
 struct LaunchCtx {
   Scratch* scratch = nullptr;    // the backend's, always set
   Mailbox* mail = nullptr;       // its device alias, always set
+  const Mailbox* mail_host = nullptr;  // the host's view of it (the skipping kernel's reports)
   LinkState* link = nullptr;     // the launch may join a linked chain (null: it runs on the given stream)
   QuietState* quiet = nullptr;   // the launch may run the skipping kernel
   bool chain = false;            // chained groups (LifeBlockParams::chain_buf) where the plan allows
@@ -303,7 +338,7 @@ GOL_LIFE_VARIANT(launch_u8_w1_add);
 // blocks over a row ring's owned rows only.  Returns the tiles launched, 0
 // (nothing launched) where the block cannot be planned that way.
 int64_t launch_bits_w1_dpp_quiet(const LifeBlockParams& p, int64_t out_rows, int T, const LaunchCtx& ctx, hipStream_t s);
-void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words);
+void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words, bool list);
 constexpr int kQuietT = 12;
 // LifeBlockParams::quiet_count, in 64-bit words a cache line apart: the
 // launch's counter, the tiles skipped by all launches, kQuietCounters
@@ -311,6 +346,37 @@ constexpr int kQuietT = 12;
 constexpr unsigned kQuietCounters = 64;
 constexpr int kQuietCountStride = 16;
 constexpr size_t kQuietCountBytes = size_t(2 + kQuietCounters) * kQuietCountStride * 8;
+// LifeBlockParams::quiet_lc, in 64-bit words (a cache line per counter or
+// slot): the append counts of the kQuietCounters sub-lists (tile %
+// kQuietCounters), the two flag-count sets (slot tile % kQuietCounters,
+// quiet::flag_words words each), the two launch-parity tickets.
+struct QuietListWords {
+  static constexpr int kAppend = 0;
+  static constexpr int kFlags = kAppend + int(kQuietCounters) * kQuietCountStride;
+  static constexpr int kFlagSet = int(kQuietCounters) * kQuietCountStride;
+  static constexpr int kTicket = kFlags + 2 * kFlagSet;
+  static constexpr int kWords = kTicket + 2 * kQuietCountStride;
+};
+// Scratch::kQuietList of a plan of `tiles` tiles: the 64-bit words, the
+// stamps, two item buffers (kQuietCounters ends + kQuietCounters sub-lists),
+// the chunk kernel's accumulators.
+// Short waves: an item runs as kQuietChunksAuto one-wave workgroups when the
+// newest reported list times that many fits QuietState::chunk_waves waves; at most kQuietChunksMax (the accumulator's arrival bits).
+constexpr int kQuietChunksMax = 24;
+constexpr int kQuietChunksAuto = 24;
+struct QuietListLayout {
+  int cap;
+  size_t stamp, items[2], acc, bytes;  // byte offsets
+  explicit QuietListLayout(int64_t tiles) {
+    cap = int((tiles + kQuietCounters - 1) / kQuietCounters);
+    const size_t item_bytes = size_t(kQuietCounters) * (1 + size_t(cap)) * 4;
+    stamp = size_t(QuietListWords::kWords) * 8;
+    items[0] = stamp + ((size_t(tiles) * 4 + 127) & ~size_t(127));
+    items[1] = items[0] + ((item_bytes + 127) & ~size_t(127));
+    acc = items[1] + ((item_bytes + 127) & ~size_t(127));
+    bytes = acc + size_t(tiles) * 8;
+  }
+};
 
 // Single-generation LDS-tiled byte-layout kernel (life_step_lds.hip).
 void launch_life_step_lds(const BlockArgs& a, int lds_rows, bool wrap, hipStream_t stream);

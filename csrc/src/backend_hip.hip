@@ -158,6 +158,10 @@ class HipBackend final : public Backend {
     quiet_tune_.on = t.i("quiet_on");
     quiet_tune_.off = std::min(t.i("quiet_off"), quiet_tune_.on);
     quiet_.seg_rows = std::max(1, t.i("quiet_rows"));
+    quiet_.list = t.i("quiet_list") != 0;  // -1: wherever the skipping kernel runs
+    quiet_.grid = std::max(-1, t.i("quiet_grid"));
+    quiet_.chunk_waves = std::max(0, t.i("quiet_chunk_waves"));
+    quiet_.chunks = t.i("quiet_chunks") == 0 ? 1 : std::max(-24, t.i("quiet_chunks"));
     if (!cu_part_.empty()) quiet_tune_.mode = 0;
   }
   static std::atomic<int>& live_backends(int dev) {
@@ -214,7 +218,7 @@ class HipBackend final : public Backend {
   void quiet_prepare(const TileGeom& g) override {
     if (quiet_tune_.mode == 0 || g.layout != Layout::Bits) return;
     GOL_ON_DEVICE();
-    hipk::prepare_bits_w1_dpp_quiet(scratch_, g.H, g.W / 32);
+    hipk::prepare_bits_w1_dpp_quiet(scratch_, g.H, g.W / 32, quiet_.list);
   }
   bool quiet_report(int64_t* seq, int64_t* tiles, int64_t* clean, int64_t* skipped_total) override {
     if (quiet_.seq == 0) return false;
@@ -234,6 +238,11 @@ class HipBackend final : public Backend {
     return true;
   }
   int quiet_tile_waves() const override { return 4; }
+  bool quiet_list() const override { return quiet_tune_.mode != 0 && quiet_.list; }
+  int64_t quiet_candidates() const override {
+    const unsigned long long r = __atomic_load_n(&mail_host_->quiet_report[2], __ATOMIC_ACQUIRE);
+    return quiet_.list && r != 0 ? int64_t(r & 0xFFFFFu) : -1;
+  }
   int64_t quiet_tiles_launched() const override { return census_.quiet_tiles; }
   std::map<std::string, int64_t> launch_paths() const override {
     std::map<std::string, int64_t> m;
@@ -642,6 +651,7 @@ class HipBackend final : public Backend {
     hipk::LaunchCtx ctx;
     ctx.scratch = &scratch_;
     ctx.mail = mail_dev_;
+    ctx.mail_host = mail_host_;
     ctx.link = linkable ? &link_ : nullptr;
     ctx.quiet = quiet ? &quiet_ : nullptr;
     // Boundary trigger: armed only if the launch runs linked (the grouped
@@ -1136,7 +1146,8 @@ uint32_t* Scratch::get(Slot slot, size_t bytes) {
     const char* name;
     bool zeroed;
   } kSlot[kSlots] = {{"chain flags", true},  {"chain slots", false}, {"link words A", true},  {"link words B", true},
-                     {"link words C", true}, {"quiet map A", true},  {"quiet map B", true},   {"quiet counters", true}};
+                     {"link words C", true}, {"quiet map A", true},  {"quiet map B", true},   {"quiet counters", true},
+                     {"quiet list", true}};
   void*& buf = buf_[slot];
   if (bytes > bytes_[slot]) {
     for (hipStream_t s : streams_)  // earlier launches may still use it

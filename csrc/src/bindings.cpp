@@ -322,6 +322,8 @@ PYBIND11_MODULE(_gol, m) {
       .def_property_readonly("quiet_blocks_skip", &Engine::quiet_blocks_skip)
       .def_property_readonly("quiet_waves_launched", &Engine::quiet_waves_launched)
       .def_property_readonly("quiet_waves_skipped", &Engine::quiet_waves_skipped)
+      .def_property_readonly("quiet_list", &Engine::quiet_list)
+      .def_property_readonly("quiet_candidates", &Engine::quiet_candidates)
       .def_property_readonly("spine_generation", &Engine::spine_generation)
       .def_property_readonly("tail_overshoots", &Engine::tail_overshoots)
       .def_property_readonly("tail_replays", &Engine::tail_replays)
@@ -402,6 +404,23 @@ PYBIND11_MODULE(_gol, m) {
     GOL_REQUIRE(nb.size() == 9, "quiet_may_skip: nine tile words (3 x 3, row-major)");
     return quiet::may_skip(nb.data());
   });
+  m.def("quiet_neighbour", &quiet::neighbour, py::arg("kcol"), py::arg("grp"), py::arg("i"), py::arg("ncolw"),
+        py::arg("nseg"));
+  m.def("quiet_marks_neighbours", &quiet::marks_neighbours);
+  m.def("quiet_flag_words", [](int T) { return quiet::flag_words(T); });
+  m.def("quiet_flag_delta", [](uint32_t old_word, uint32_t new_word, int w) {
+    return (unsigned long long)quiet::flag_delta(old_word, new_word, w);
+  });
+  m.def("quiet_flag_levels", [](unsigned long long count, int w) { return quiet::flag_levels(count, w); });
+  py::class_<quiet::ListModel>(m, "QuietListModel")
+      .def(py::init<int, int, int>(), py::arg("ncolw"), py::arg("nseg"), py::arg("T"))
+      .def("block", &quiet::ListModel::block, py::arg("fresh"), py::arg("follow"))
+      .def("words", &quiet::ListModel::words)
+      .def("words_before", &quiet::ListModel::words_before)
+      .def("launched", &quiet::ListModel::launched)
+      .def("candidates", &quiet::ListModel::candidates)
+      .def("flags", &quiet::ListModel::flags)
+      .def("flag_counts", &quiet::ListModel::flag_counts);
   py::class_<quiet::Launch>(m, "QuietLaunch")
       .def(py::init([](std::uintptr_t in, std::uintptr_t out, int T, int64_t row_lo, int64_t row_hi, int64_t pitch,
                        int ncolw, int nseg, int seg_rows, int seg_rem, int grp_q, int wrap_w) {

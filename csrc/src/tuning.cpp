@@ -41,6 +41,22 @@ const std::vector<TuningKey>& tuning_keys() {
       {"quiet_off", "GOL_QUIET_OFF", "35", 'i', "tune", "quiet_skip auto: percent of clean tiles below which it stops"},
       {"quiet_rows", "GOL_QUIET_ROWS", "96", 'i', "tune",
        "output rows per 4-wave group (one tile) of the skipping kernel's plan"},
+      {"quiet_list", "GOL_QUIET_LIST", "-1", 'i', "tune",
+       "skipping blocks launch only the tiles next to the last block's activity (the candidate list): -1 wherever "
+       "the skipping kernel runs, 0 never (one workgroup per tile), 1 on"},
+      {"quiet_grid", "GOL_QUIET_GRID", "0", 'i', "tune",
+       "workgroups of a candidate-list launch of 4-wave groups: 0 (default) one per tile of the plan - not a size "
+       "chosen from the list's length: the groups beyond the list return at once, measured faster than the kernel "
+       "that may loop; -1 the size chosen from the newest reported list length (twice that and 256) and n a forced "
+       "size, both with the looping kernel, whose groups take further items from a ticket; with short waves: items' "
+       "worth of waves"},
+      {"quiet_chunks", "GOL_QUIET_CHUNKS", "-1", 'i', "tune",
+       "one-wave workgroups per item of a candidate-list launch (short waves: each runs a part of the tile's rows "
+       "with a prologue of its own, no LDS, no barrier): -1 24 where 24 times the newest reported list length is "
+       "at most quiet_chunk_waves, else 1 (-n: the same with n for 24); 1 off (a 4-wave group per item); n forced "
+       "for every list launch, at most 24"},
+      {"quiet_chunk_waves", "GOL_QUIET_CHUNK_WAVES", "1024", 'i', "tune",
+       "quiet_chunks auto: the most one-wave workgroups a list launch is split into (1024: one per SIMD)"},
       {"lazy_tail", "GOL_LAZY_TAIL", "-1", 'i', "tune",
        "a run whose last epoch is shorter than a block runs one full block instead and reports its limit; the "
        "generations beyond it carry into the next run, and a read of the grid rewinds and replays the remainder "

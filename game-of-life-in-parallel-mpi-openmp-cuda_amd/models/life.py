@@ -265,6 +265,10 @@ class Simulation:
                                  "skip": self._eng.quiet_blocks_skip},
                 "quiet_waves_launched": self._eng.quiet_waves_launched,
                 "quiet_waves_skipped": self._eng.quiet_waves_skipped,
+                # The candidate list (tuning quiet_list): on or off, and the tiles the newest
+                # finished launch listed for its successor (-1: none reported yet).
+                "quiet_list": bool(self._eng.quiet_list),
+                "quiet_candidates": self._eng.quiet_candidates,
                 # Lazy tail (tuning lazy_tail): the generation the block chain has reached (up to
                 # tmax - 1 past `generation` after a run that ended on a full block), runs that
                 # ended that way, and how many of those blocks a read of the grid had to replay.
