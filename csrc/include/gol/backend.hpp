@@ -190,6 +190,11 @@ class Backend {
   // Tiles that are not launched count as launched, clean and skipped above.
   virtual bool quiet_list() const { return false; }
   virtual int64_t quiet_candidates() const { return -1; }
+  // The column kernel (tuning quiet_cols): whether list launches may run it,
+  // and over all its finished launches the word columns it computed and the
+  // owned word columns of the tiles it computed them in.
+  virtual bool quiet_cols() const { return false; }
+  virtual void quiet_cols_counts(int64_t* computed, int64_t* of_tiles) const { *computed = *of_tiles = 0; }
   // Whether run_block evaluates `rule` (BlockArgs::rule) on tiles of this
   // layout.  The CPU backend runs any rule without B0; the HIP backend the
   // rules compiled from csrc/kernels/life_rules.def.  unsupported_rule() is

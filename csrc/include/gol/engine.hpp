@@ -209,6 +209,14 @@ class Engine {
   int64_t quiet_waves_skipped();
   bool quiet_list() const { return quiet_.mode != 0 && be_->quiet_list(); }
   int64_t quiet_candidates() const { return be_->quiet_candidates(); }
+  bool quiet_cols() const { return quiet_.mode != 0 && be_->quiet_cols(); }
+  // {columns computed, columns of the tiles they were computed in} (complete once a run has returned).
+  std::vector<int64_t> quiet_cols_counts() {
+    quiet_poll();
+    int64_t a = 0, b = 0;
+    be_->quiet_cols_counts(&a, &b);
+    return {a, b};
+  }
   // Storage-frame drift (cells, mod W) left by drifting kernels
   // (Backend::drifts): stored column x holds true column x - drift.
   int64_t drift() const { return drift_; }

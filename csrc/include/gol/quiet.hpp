@@ -33,6 +33,7 @@ namespace quiet {
 
 constexpr uint32_t kFlagMask = 0xFFFFu;
 constexpr uint32_t kDirty = 1u << 16, kTop = 1u << 17, kBot = 1u << 18, kLeft = 1u << 19, kRight = 1u << 20;
+constexpr uint32_t kCols = 1u << 21;  // the tile's column records are valid (below: Column records)
 
 // nb[3 * r + c]: the previous block's words of the tile (nb[4]) and its eight
 // neighbours on the torus of tiles, row r - 1 below/above (0 = above), strip
@@ -58,7 +59,72 @@ GOL_HD inline bool may_skip(const uint32_t* nb) {
 // (an oscillator or a glider inside a tile) leaves the tiles around it the
 // inputs they had.  A tile that computed is launched in the next block in any
 // case, where it writes the other map.
-GOL_HD inline bool marks_neighbours(uint32_t old_word, uint32_t new_word) { return old_word != new_word; }
+GOL_HD inline bool marks_neighbours(uint32_t old_word, uint32_t new_word) {
+  return ((old_word ^ new_word) & ~kCols) != 0u;  // kCols says nothing about the tile's cells
+}
+
+// ---- Column records (tuning quiet_cols) ----
+// What holds for a tile holds for each of its word columns: T <= 16 < 32
+// cells, so the light cone of word column c over the tile's rows is columns
+// c - 1 .. c + 1 over those rows and T rows above and below.  Beside its word a
+// tile may publish one record per lane column (kColLanes of them: lane 0 and
+// the lanes past the strip's owned columns are not used), the bits of a tile
+// word restricted to that column: its level flags, kDirty, kTop, kBot.  The
+// tile word is the OR of the owned columns' records, kLeft / kRight the dirty
+// bits of the first and last owned column.  kCols in a tile word of a map:
+// that map holds the tile's records of the block that published the word.
+// Records are kept per row band of the tile (the column kernel's units), a
+// reader ORs the bands.
+constexpr int kColLanes = 64;
+constexpr uint32_t kColMask = kFlagMask | kDirty | kTop | kBot;
+// The record every column of a tile without valid records is taken to have.
+GOL_HD inline uint32_t col_standin(uint32_t word) { return word & (kDirty | kTop | kBot); }
+// Whether a column makes the columns beside it (and itself) recompute: above,
+// same, below are its records in the tile above, the tile and the tile below.
+GOL_HD inline bool col_source(uint32_t above, uint32_t same, uint32_t below) {
+  return ((same & kDirty) | (above & kBot) | (below & kTop)) != 0u;
+}
+// src: bit j = col_source of lane column j of the strip, j = 1 .. own; bit 0
+// that of the last owned column of the strip to the left, bit own + 1 that of
+// the first owned column of the strip to the right.  Returns the owned
+// columns whose cone holds a source.
+GOL_HD inline uint64_t window_spread(uint64_t src, int own) {
+  const uint64_t owned = ((own >= 63 ? ~0ull : (1ull << (own + 1)) - 1ull)) & ~1ull;
+  return (src | src << 1 | src >> 1) & owned;
+}
+// The columns of the centre tile to recompute.  rec[i]: the kColLanes records
+// of tile i of the neighbourhood (as may_skip's nb[], bands ORed), or null
+// where words[i] lacks kCols (col_standin then).  own_l, own, own_r: owned
+// columns of the strip to the left, the tile's strip and the strip to the
+// right.  A tile whose own records are not valid recomputes every column.
+GOL_HD inline uint64_t window(const uint32_t* const* rec, const uint32_t* words, int own_l, int own, int /*own_r*/) {
+  const uint64_t owned = window_spread(~0ull, own);
+  if (!(words[4] & kCols) || !rec[4]) return owned;
+  const auto at = [&](int i, int j) { return (words[i] & kCols) && rec[i] ? rec[i][j] : col_standin(words[i]); };
+  uint64_t src = 0;
+  if (col_source(at(0, own_l), at(3, own_l), at(6, own_l))) src |= 1ull;
+  for (int j = 1; j <= own; ++j)
+    if (col_source(at(1, j), at(4, j), at(7, j))) src |= 1ull << j;
+  if (col_source(at(2, 1), at(5, 1), at(8, 1))) src |= 1ull << (own + 1);
+  return window_spread(src, own);
+}
+// The column kernel computes whole groups of `g` adjacent owned columns
+// (group q: lane columns 1 + q g ...): the groups the window meets, one bit
+// each, and the columns of those groups.  A computing tile whose window is
+// empty (may_skip reads a corner tile more coarsely than the records do)
+// computes its first group.
+GOL_HD inline uint32_t window_groups(uint64_t win, int own, int g) {
+  uint32_t hit = 0;
+  for (int q = 0; q * g < own; ++q)
+    if ((win >> (1 + q * g)) & ((1ull << g) - 1ull)) hit |= 1u << q;
+  return hit ? hit : 1u;
+}
+GOL_HD inline uint64_t group_columns(uint32_t hit, int own, int g) {
+  uint64_t m = 0;
+  for (int q = 0; q * g < own; ++q)
+    if ((hit >> q) & 1u) m |= ((1ull << g) - 1ull) << (1 + q * g);
+  return m & window_spread(~0ull, own);
+}
 
 // Tile i (0..8, row-major as may_skip's nb[]) of the neighbourhood of tile
 // (strip kcol, group grp) on the torus of ncolw x nseg tiles.  The relation is
@@ -218,6 +284,13 @@ class ListModel {
     cur_ ^= 1;
     return computed;
   }
+  // The tiles the next block launches (follow: as block()'s).
+  std::vector<int> items(bool follow) const {
+    if (follow && !all_) return list_;
+    std::vector<int> v(stamp_.size());
+    for (size_t t = 0; t < v.size(); ++t) v[t] = int(t);
+    return v;
+  }
   const std::vector<uint32_t>& words() const { return map_[cur_]; }       // the map the last block wrote
   const std::vector<uint32_t>& words_before() const { return map_[cur_ ^ 1]; }
   int64_t launched() const { return launched_; }                          // tiles the last block launched
@@ -243,6 +316,88 @@ class ListModel {
   std::vector<uint32_t> map_[2], stamp_;
   std::vector<int> list_;
   std::vector<unsigned long long> counts_;
+};
+
+// Host model of the column kernel on top of the list: per map, every tile's
+// column records (bands ORed) and whether they are valid.  `fresh[t *
+// kColLanes + j]` is the record column j of tile t publishes if it is
+// computed in this block; `cols` false is a launch of the bodies that publish
+// no records.  A computing tile of a column launch computes the groups of `g`
+// columns its window meets and keeps the other columns' records; its word is
+// the OR of both - which exactness makes the OR of all its fresh records.
+class ColsModel {
+ public:
+  ColsModel(int ncolw, int nseg, int T, int last_own, int g)
+      : list_(ncolw, nseg, T), ncolw_(ncolw), nseg_(nseg), last_own_(last_own), g_(g) {
+    for (int m = 0; m < 2; ++m) {
+      rec_[m].assign(size_t(ncolw) * nseg * kColLanes, 0u);
+      valid_[m].assign(size_t(ncolw) * nseg, 0);
+    }
+  }
+  int own(int kcol) const { return kcol == ncolw_ - 1 ? last_own_ : kColLanes - 2; }
+  // The word of a tile from its columns' records.
+  uint32_t word_of(const uint32_t* rec, int kcol) const {
+    uint32_t w = 0;
+    for (int j = 1; j <= own(kcol); ++j) w |= rec[j];
+    if (rec[1] & kDirty) w |= kLeft;
+    if (rec[own(kcol)] & kDirty) w |= kRight;
+    return w;
+  }
+  // The window of tile t on the map the last block wrote.
+  uint64_t window_of(int t) const {
+    const int kcol = t / nseg_, grp = t % nseg_;
+    const uint32_t* rec[9];
+    uint32_t words[9];
+    for (int i = 0; i < 9; ++i) {
+      const int n = neighbour(kcol, grp, i, ncolw_, nseg_);
+      words[i] = (list_.words()[size_t(n)] & ~kCols) | (valid_[cur_][size_t(n)] ? kCols : 0u);
+      rec[i] = valid_[cur_][size_t(n)] ? &rec_[cur_][size_t(n) * kColLanes] : nullptr;
+    }
+    return window(rec, words, own((kcol + ncolw_ - 1) % ncolw_), own(kcol), own((kcol + 1) % ncolw_));
+  }
+  // Runs one block; returns per tile the columns computed (0: skipped or not launched).
+  std::vector<uint64_t> block(const std::vector<uint32_t>& fresh, bool follow, bool cols) {
+    const int tiles = ncolw_ * nseg_;
+    const bool col_launch = cols && follow;
+    std::vector<uint32_t> words(size_t(tiles), 0u), nrec(rec_[cur_ ^ 1]);
+    std::vector<uint64_t> done(size_t(tiles), 0ull);
+    const std::vector<int> items = list_.items(follow);
+    for (int t : items) {
+      const int kcol = t / nseg_;
+      uint64_t cols_done = window_spread(~0ull, own(kcol));
+      if (col_launch) cols_done = group_columns(window_groups(window_of(t), own(kcol), g_), own(kcol), g_);
+      for (int j = 1; j <= own(kcol); ++j) {
+        const size_t at = size_t(t) * kColLanes + j;
+        nrec[at] = (cols_done >> j) & 1ull ? fresh[at] : rec_[cur_][at];
+      }
+      words[size_t(t)] = word_of(&nrec[size_t(t) * kColLanes], kcol);
+      done[size_t(t)] = cols_done;
+    }
+    const std::vector<int> computed = list_.block(words, follow);
+    std::vector<char> comp(size_t(tiles), 0);
+    for (int t : computed) comp[size_t(t)] = 1;
+    for (int t : items) {
+      if (comp[size_t(t)]) {
+        valid_[cur_ ^ 1][size_t(t)] = col_launch;
+      } else {  // skipped: the word again, and (a column launch) its records
+        valid_[cur_ ^ 1][size_t(t)] = col_launch && valid_[cur_][size_t(t)];
+        for (int j = 0; j < kColLanes; ++j) nrec[size_t(t) * kColLanes + j] = rec_[cur_][size_t(t) * kColLanes + j];
+        done[size_t(t)] = 0ull;
+      }
+    }
+    rec_[cur_ ^ 1] = nrec;
+    cur_ ^= 1;
+    return done;
+  }
+  const ListModel& list() const { return list_; }
+  const std::vector<uint32_t>& records() const { return rec_[cur_]; }
+  bool valid(int t) const { return valid_[cur_][size_t(t)] != 0; }
+
+ private:
+  ListModel list_;
+  int ncolw_, nseg_, last_own_, g_, cur_ = 0;
+  std::vector<uint32_t> rec_[2];
+  std::vector<char> valid_[2];
 };
 #endif  // !__HIP_DEVICE_COMPILE__
 

@@ -1,6 +1,6 @@
 // life_block variant: the quiet-tile skipping kernel (life_quiet_impl.hpp) on
 // BitsIO<1, kXlaneDpp>, T = 12 in 4-wave groups.
-#include "life_quiet_impl.hpp"
+#include "life_quiet_cols_impl.hpp"
 
 namespace gol {
 namespace hipk {
@@ -8,6 +8,12 @@ namespace hipk {
 namespace {
 constexpr int kQuietM = 4;
 using QuietIO = lb::BitsIO<1, kXlaneDpp>;
+constexpr int kColBandRows = 64 - 2 * kQuietT;
+
+template <int G>
+void launch_cols(const LifeBlockParams& p, int64_t grid, hipStream_t s) {
+  hipLaunchKernelGGL((lb::life_quiet_cols_kernel<kQuietT, QuietIO, G>), dim3(unsigned(grid)), dim3(64), 0, s, p);
+}
 }  // namespace
 
 // Up front, outside any timed run: the maps and counters of a tile of H rows
@@ -26,6 +32,15 @@ void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words, bool 
     (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, true, false>));
     (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, true, true>));
     (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_chunk_kernel<kQuietT, QuietIO>));
+    // The column kernel's records: at most this many (tile, band) pairs,
+    // whatever the plan (a band per kColBandRows rows and one more per tile).
+    const int64_t strips = ceil_div(words, int64_t(lb::wave_out_words<kXlaneDpp, 1>()));
+    const size_t rec_bytes = size_t(strips * (H / kColBandRows + 1) + tiles + tiles / 16) * quiet::kColLanes * 4;
+    scratch.get(Scratch::kQuietRecA, rec_bytes);
+    scratch.get(Scratch::kQuietRecB, rec_bytes);
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_cols_kernel<kQuietT, QuietIO, 2>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_cols_kernel<kQuietT, QuietIO, 4>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_cols_kernel<kQuietT, QuietIO, 8>));
   } else {
     (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&lb::life_quiet_kernel<kQuietT, QuietIO, kQuietM, false>));
   }
@@ -100,7 +115,28 @@ int64_t launch_bits_w1_dpp_quiet(const LifeBlockParams& p0, int64_t out_rows, in
     // which covers any list - the groups beyond it return on their first load,
     // and the kernel needs no loop.  quiet_grid > 0 forces a grid, -1 takes
     // the size above; both run the looping kernel, right with any grid.
-    if (K > 1) {
+    // The column kernel (tuning quiet_cols): a listed launch - it reads a list
+    // and the last launch's words - whose tiles fit its bands; forced, or by
+    // default where the reported list is at most quiet_col_items long and
+    // neither quiet_chunks nor quiet_grid forces another body.  Its units
+    // stride over any grid, so it takes the short waves' sizing.
+    const int bands = int(ceil_div(int64_t(p.seg_rows) + (p.seg_rem ? 1 : 0), int64_t(kColBandRows)));
+    const bool cols = listed && bands <= kQuietColBandsMax &&
+                      (Q->cols > 0 || (Q->cols < 0 && Q->chunks < 0 && Q->grid == 0 && reported >= 0 && reported <= Q->col_items));
+    Q->cols_last = cols;
+    if (cols) {
+      const size_t rec_bytes = size_t(tiles) * bands * quiet::kColLanes * 4;
+      uint32_t* const recs[2] = {ctx.scratch->get(Scratch::kQuietRecA, rec_bytes),
+                                 ctx.scratch->get(Scratch::kQuietRecB, rec_bytes)};
+      p.quiet_rec_prev = recs[Q->cur];
+      p.quiet_rec_next = recs[next];
+      p.quiet_bands = bands;
+      Q->chunks_last = 1;
+      grid = std::max<int64_t>(1, (Q->grid > 0 ? std::min<int64_t>(Q->grid, tiles) : sized) * kQuietChunksAuto);
+      if (Q->col_group <= 2) launch_cols<2>(p, grid, s);
+      else if (Q->col_group >= 8) launch_cols<8>(p, grid, s);
+      else launch_cols<4>(p, grid, s);
+    } else if (K > 1) {
       p.quiet_chunks = K;
       grid = (Q->grid > 0 ? std::min<int64_t>(Q->grid, tiles) : sized) * K;
       hipLaunchKernelGGL((lb::life_quiet_chunk_kernel<kQuietT, IO>), dim3(unsigned(grid)), dim3(64), 0, s, p);

@@ -124,6 +124,13 @@ struct LifeBlockParams {
   // launches).
   int quiet_chunks;
   unsigned long long* quiet_acc;
+  // The column kernel (life_quiet_cols_kernel; gol/quiet.hpp, Column records):
+  // the records that go with quiet_prev / quiet_next, quiet::kColLanes per
+  // (tile, row band), quiet_bands bands per tile.  Null in launches of the
+  // other bodies, which publish words without quiet::kCols.
+  const uint32_t* quiet_rec_prev;
+  uint32_t* quiet_rec_next;
+  int quiet_bands;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -228,13 +235,18 @@ struct QuietState {
   int chunks = -1;                 // tuning quiet_chunks: -1 by the reported list length, 1 off, n forced
   int64_t chunk_waves = 1024;      // tuning quiet_chunk_waves: most one-wave workgroups an automatic choice makes
   int chunks_last = 1;             // one-wave workgroups per item of the last launch (1: the grouped kernel)
+  // The column kernel (tuning quiet_cols, quiet_col_group, quiet_col_items).
+  int cols = 0;                    // 0 off, -1 by the reported list length, 1 every listed launch
+  int col_group = 4;               // owned word columns per unit: 2, 4 or 8
+  int64_t col_items = 42;          // quiet_cols auto: the longest reported list the column kernel runs
+  bool cols_last = false;          // the last launch ran the column kernel
 };
 
 // Words the kernels write for the host: one fine-grained pinned host
 // allocation, written through its device alias and read without a copy.
 struct Mailbox {
   uint32_t err[4];  // LifeBlockParams::err: the code (check_device_errors), then a give-up's diagnostics
-  unsigned long long quiet_report[3];  // LifeBlockParams::quiet_report
+  unsigned long long quiet_report[5];  // LifeBlockParams::quiet_report
 };
 
 // Device memory that persists across launches, owned by the backend: one
@@ -245,7 +257,7 @@ class Scratch {
  public:
   enum Slot {
     kChainFlags, kChainSlots, kLinkWordsA, kLinkWordsB, kLinkWordsC, kQuietMapA, kQuietMapB, kQuietCounters,
-    kQuietList, kSlots
+    kQuietList, kQuietRecA, kQuietRecB, kSlots
   };
   static constexpr Slot kLinkWords[3] = {kLinkWordsA, kLinkWordsB, kLinkWordsC};  // LinkState::flags
   // The two compute streams (the second may be null), which both drain before
@@ -338,6 +350,9 @@ GOL_LIFE_VARIANT(launch_u8_w1_add);
 // blocks over a row ring's owned rows only.  Returns the tiles launched, 0
 // (nothing launched) where the block cannot be planned that way.
 int64_t launch_bits_w1_dpp_quiet(const LifeBlockParams& p, int64_t out_rows, int T, const LaunchCtx& ctx, hipStream_t s);
+// Output rows per row band of the column kernel (64 lanes less the cone), and
+// the most bands per tile it is compiled to keep records for.
+constexpr int kQuietColBandsMax = 4;
 void prepare_bits_w1_dpp_quiet(Scratch& scratch, int64_t H, int64_t words, bool list);
 constexpr int kQuietT = 12;
 // LifeBlockParams::quiet_count, in 64-bit words a cache line apart: the
@@ -345,7 +360,11 @@ constexpr int kQuietT = 12;
 // first-level counters.
 constexpr unsigned kQuietCounters = 64;
 constexpr int kQuietCountStride = 16;
-constexpr size_t kQuietCountBytes = size_t(2 + kQuietCounters) * kQuietCountStride * 8;
+constexpr size_t kQuietCountBytes = size_t(4 + kQuietCounters) * kQuietCountStride * 8;
+// After the first-level counters, the column kernel's totals over all
+// launches: word columns it computed, and owned word columns of the tiles it
+// computed them in (quiet_report[3], [4]).
+constexpr int kQuietColsComputed = 2 + int(kQuietCounters), kQuietColsOfTiles = 3 + int(kQuietCounters);
 // LifeBlockParams::quiet_lc, in 64-bit words (a cache line per counter or
 // slot): the append counts of the kQuietCounters sub-lists (tile %
 // kQuietCounters), the two flag-count sets (slot tile % kQuietCounters,

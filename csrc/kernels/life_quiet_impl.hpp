@@ -25,7 +25,10 @@
 //     word, summed by the group that ends the launch (quiet_complete);
 //   * short waves (life_quiet_chunk_kernel, tuning quiet_chunks): where the
 //     list is short, every item runs as K one-wave workgroups of the classic
-//     body instead of one 4-wave group.
+//     body instead of one 4-wave group;
+//   * the column kernel (life_quiet_cols_impl.hpp, tuning quiet_cols): a
+//     computing tile recomputes only the word columns near activity.  The
+//     bodies here publish no column records: their words lack quiet::kCols.
 // No folded strip, no chained or linked groups: the plan is regular, so the
 // tile of block (strip, group) is the same rows and words in every launch of
 // the same plan (quiet::may_follow).  No group ever waits for another.
@@ -70,7 +73,9 @@ struct QuietWriter {
 // do not queue on one word: item i adds itself to counter i % 64 (a cache line
 // each); the one that completes a counter adds its sum to the launch's
 // counter, and the one that completes that (returns true, the totals in
-// `tot`) resets it.  n_items: the items of the launch (a tile each).
+// `tot`) resets it.  n_items: the items of the launch (a tile each); a launch
+// of at most kQuietCounters items counts on the launch's counter at once (one
+// atomic round trip less on the chain of the tile that ends the launch).
 __device__ __forceinline__ bool quiet_count(const LifeBlockParams& p, int item, int n_items, bool clean, bool skipped,
                                             unsigned long long& tot) {
   const auto add = [](unsigned long long* c, unsigned long long v) {
@@ -79,9 +84,16 @@ __device__ __forceinline__ bool quiet_count(const LifeBlockParams& p, int item, 
   const auto put = [](unsigned long long* c, unsigned long long v) {
     __hip_atomic_store(c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
+  const unsigned long long mine = 1ull | (clean ? 1ull << 20 : 0ull) | (skipped ? 1ull << 40 : 0ull);
+  if (unsigned(n_items) <= kQuietCounters) {  // nothing to spread: every first-level counter would take one item
+    tot = add(p.quiet_count, mine);
+    if ((tot & 0xFFFFFull) != unsigned(n_items)) return false;
+    put(p.quiet_count, 0ull);
+    return true;
+  }
   const unsigned slot = unsigned(item) % kQuietCounters;
   unsigned long long* const c1 = p.quiet_count + kQuietCountStride * (2 + slot);
-  tot = add(c1, 1ull | (clean ? 1ull << 20 : 0ull) | (skipped ? 1ull << 40 : 0ull));
+  tot = add(c1, mine);
   if ((tot & 0xFFFFFull) != (unsigned(n_items) - slot + kQuietCounters - 1) / kQuietCounters) return false;
   put(c1, 0ull);
   tot = add(p.quiet_count, tot);
@@ -113,7 +125,8 @@ __device__ __forceinline__ void quiet_publish(const LifeBlockParams& p, unsigned
 // level L (the flag counts: exact, launched or not); the other flag-count set
 // and the next launch's ticket are zeroed.  Everything another group handed
 // over is read with 64-bit agent-scope atomics, as it was written.
-template <int T>
+// COLS (the column kernel): its totals reach the host as well.
+template <int T, bool COLS = false>
 __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigned long long tot, int n_items, int lane) {
   using LW = QuietListWords;
   unsigned long long* const cnt = p.quiet_lc + LW::kAppend + lane * kQuietCountStride;
@@ -143,6 +156,14 @@ __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigne
     __hip_atomic_store(p.quiet_lc + LW::kTicket + ((p.quiet_seq + 1) & 1u) * kQuietCountStride, 0ull, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long rest = (unsigned long long)(p.ncolw * p.nseg - n_items);
+    if constexpr (COLS) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        __hip_atomic_store(p.quiet_report + 3 + i,
+                           __hip_atomic_load(p.quiet_count + kQuietCountStride * (kQuietColsComputed + i), __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     // A launch with nothing to follow appended nothing: the next block runs every tile.
     quiet_publish<true>(p, ((tot >> 20) & 0xFFFFFull) + rest, (tot >> 40) + rest,
                         p.quiet_prev ? n_next : uint32_t(p.ncolw * p.nseg));
@@ -151,7 +172,7 @@ __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigne
 
 // A whole wave counts item `item` of a list launch (lane 0 does) and ends the
 // launch if it was the last.
-template <int T>
+template <int T, bool COLS = false>
 __device__ __forceinline__ void quiet_done_list(const LifeBlockParams& p, int item, int n_items, bool clean, bool skipped,
                                                 int lane) {
   unsigned long long tot = 0;
@@ -159,7 +180,7 @@ __device__ __forceinline__ void quiet_done_list(const LifeBlockParams& p, int it
   if (lane == 0) fin = quiet_count(p, item, n_items, clean, skipped, tot) ? 1 : 0;
   if (__builtin_amdgcn_readfirstlane(fin)) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(tot)), hi = __builtin_amdgcn_readfirstlane(uint32_t(tot >> 32));
-    quiet_complete<T>(p, (unsigned long long)hi << 32 | lo, n_items, lane);
+    quiet_complete<T, COLS>(p, (unsigned long long)hi << 32 | lo, n_items, lane);
   }
 }
 
@@ -269,7 +290,7 @@ __device__ __forceinline__ void quiet_tile(const LifeBlockParams& p, const int b
           const uint32_t mask = nb[4] & quiet::kFlagMask;
           if (ch && lane < T && ((mask >> lane) & 1u)) ch[lane] = 1u;
         }
-        if (lane == 0) p.quiet_next[blk] = nb[4];
+        if (lane == 0) p.quiet_next[blk] = nb[4] & ~quiet::kCols;  // this body copies no column records
         if constexpr (LIST) {
           if (!p.quiet_items) quiet_recount<T>(p, blk, nb[4], lane);
         }
@@ -478,7 +499,7 @@ __global__ __launch_bounds__(64) void life_quiet_chunk_kernel(const LifeBlockPar
       for (int i = 0; i < 9; ++i) nb[i] = __builtin_amdgcn_readlane(w, i);
       if (quiet::may_skip(nb)) {
         if (chunk == 0) {
-          if (lane == 0) p.quiet_next[blk] = nb[4];
+          if (lane == 0) p.quiet_next[blk] = nb[4] & ~quiet::kCols;  // this body copies no column records
           if (!p.quiet_items) quiet_recount<T>(p, blk, nb[4], lane);
           quiet_done_list<T>(p, item, n_items, true, true, lane);
         }

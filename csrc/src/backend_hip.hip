@@ -162,6 +162,9 @@ class HipBackend final : public Backend {
     quiet_.grid = std::max(-1, t.i("quiet_grid"));
     quiet_.chunk_waves = std::max(0, t.i("quiet_chunk_waves"));
     quiet_.chunks = t.i("quiet_chunks") == 0 ? 1 : std::max(-24, t.i("quiet_chunks"));
+    quiet_.cols = std::max(-1, std::min(1, t.i("quiet_cols")));
+    quiet_.col_group = t.i("quiet_col_group") <= 2 ? 2 : t.i("quiet_col_group") >= 8 ? 8 : 4;
+    quiet_.col_items = std::max(0, t.i("quiet_col_items"));
     if (!cu_part_.empty()) quiet_tune_.mode = 0;
   }
   static std::atomic<int>& live_backends(int dev) {
@@ -244,6 +247,11 @@ class HipBackend final : public Backend {
     return quiet_.list && r != 0 ? int64_t(r & 0xFFFFFu) : -1;
   }
   int64_t quiet_tiles_launched() const override { return census_.quiet_tiles; }
+  bool quiet_cols() const override { return quiet_list() && quiet_.cols != 0; }
+  void quiet_cols_counts(int64_t* computed, int64_t* of_tiles) const override {
+    *computed = int64_t(__atomic_load_n(&mail_host_->quiet_report[3], __ATOMIC_ACQUIRE));
+    *of_tiles = int64_t(__atomic_load_n(&mail_host_->quiet_report[4], __ATOMIC_ACQUIRE));
+  }
   std::map<std::string, int64_t> launch_paths() const override {
     std::map<std::string, int64_t> m;
     for (int i = 0; i < hipk::kLaunchPaths; ++i) m[hipk::kLaunchPathNames[i]] = census_.launches[i];
@@ -1147,7 +1155,7 @@ uint32_t* Scratch::get(Slot slot, size_t bytes) {
     bool zeroed;
   } kSlot[kSlots] = {{"chain flags", true},  {"chain slots", false}, {"link words A", true},  {"link words B", true},
                      {"link words C", true}, {"quiet map A", true},  {"quiet map B", true},   {"quiet counters", true},
-                     {"quiet list", true}};
+                     {"quiet list", true},   {"quiet records A", true}, {"quiet records B", true}};
   void*& buf = buf_[slot];
   if (bytes > bytes_[slot]) {
     for (hipStream_t s : streams_)  // earlier launches may still use it

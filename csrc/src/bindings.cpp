@@ -324,6 +324,8 @@ PYBIND11_MODULE(_gol, m) {
       .def_property_readonly("quiet_waves_skipped", &Engine::quiet_waves_skipped)
       .def_property_readonly("quiet_list", &Engine::quiet_list)
       .def_property_readonly("quiet_candidates", &Engine::quiet_candidates)
+      .def_property_readonly("quiet_cols", &Engine::quiet_cols)
+      .def("quiet_cols_counts", &Engine::quiet_cols_counts)
       .def_property_readonly("spine_generation", &Engine::spine_generation)
       .def_property_readonly("tail_overshoots", &Engine::tail_overshoots)
       .def_property_readonly("tail_replays", &Engine::tail_replays)
@@ -421,6 +423,41 @@ PYBIND11_MODULE(_gol, m) {
       .def("candidates", &quiet::ListModel::candidates)
       .def("flags", &quiet::ListModel::flags)
       .def("flag_counts", &quiet::ListModel::flag_counts);
+  // The column records (tuning quiet_cols).
+  m.attr("QUIET_COLS") = quiet::kCols;
+  m.attr("QUIET_COL_LANES") = quiet::kColLanes;
+  m.def("quiet_col_standin", &quiet::col_standin);
+  m.def("quiet_col_source", &quiet::col_source, py::arg("above"), py::arg("same"), py::arg("below"));
+  m.def("quiet_window_spread", [](unsigned long long src, int own) { return (unsigned long long)quiet::window_spread(src, own); });
+  m.def("quiet_window_groups", [](unsigned long long win, int own, int g) { return quiet::window_groups(win, own, g); });
+  m.def("quiet_group_columns",
+        [](uint32_t hit, int own, int g) { return (unsigned long long)quiet::group_columns(hit, own, g); });
+  // rec[i]: the records of tile i of the neighbourhood (empty: none valid), words[i] its word.
+  m.def("quiet_window",
+        [](const std::vector<std::vector<uint32_t>>& rec, const std::vector<uint32_t>& words, int own_l, int own, int own_r) {
+          GOL_REQUIRE(rec.size() == 9 && words.size() == 9, "quiet_window: nine tiles (3 x 3, row-major)");
+          const uint32_t* r[9];
+          for (int i = 0; i < 9; ++i) {
+            GOL_REQUIRE(rec[i].empty() || rec[i].size() == size_t(quiet::kColLanes), "quiet_window: 64 records per tile");
+            r[i] = rec[i].empty() ? nullptr : rec[i].data();
+          }
+          return (unsigned long long)quiet::window(r, words.data(), own_l, own, own_r);
+        },
+        py::arg("rec"), py::arg("words"), py::arg("own_l"), py::arg("own"), py::arg("own_r"));
+  py::class_<quiet::ColsModel>(m, "QuietColsModel")
+      .def(py::init<int, int, int, int, int>(), py::arg("ncolw"), py::arg("nseg"), py::arg("T"), py::arg("last_own"),
+           py::arg("g"))
+      .def("block", [](quiet::ColsModel& c, const std::vector<uint32_t>& fresh, bool follow, bool cols) {
+             std::vector<unsigned long long> out;
+             for (uint64_t v : c.block(fresh, follow, cols)) out.push_back(v);
+             return out;
+           },
+           py::arg("fresh"), py::arg("follow"), py::arg("cols"))
+      .def("window_of", [](const quiet::ColsModel& c, int t) { return (unsigned long long)c.window_of(t); })
+      .def("words", [](const quiet::ColsModel& c) { return c.list().words(); })
+      .def("candidates", [](const quiet::ColsModel& c) { return c.list().candidates(); })
+      .def("records", &quiet::ColsModel::records)
+      .def("valid", &quiet::ColsModel::valid);
   py::class_<quiet::Launch>(m, "QuietLaunch")
       .def(py::init([](std::uintptr_t in, std::uintptr_t out, int T, int64_t row_lo, int64_t row_hi, int64_t pitch,
                        int ncolw, int nseg, int seg_rows, int seg_rem, int grp_q, int wrap_w) {

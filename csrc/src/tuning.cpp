@@ -57,6 +57,16 @@ const std::vector<TuningKey>& tuning_keys() {
        "for every list launch, at most 24"},
       {"quiet_chunk_waves", "GOL_QUIET_CHUNK_WAVES", "1024", 'i', "tune",
        "quiet_chunks auto: the most one-wave workgroups a list launch is split into (1024: one per SIMD)"},
+      {"quiet_cols", "GOL_QUIET_COLS", "0", 'i', "tune",
+       "the column kernel for candidate-list launches (a computing tile recomputes only the groups of word columns "
+       "whose light cone changed in the last block; lanes are rows, one-wave workgroups per row band and column "
+       "group): 0 (default) off - the 4-wave groups and short waves alone; measured on par with them, not faster; "
+       "-1 where the newest reported list is at most quiet_col_items long and neither quiet_chunks nor quiet_grid "
+       "forces another body; 1 every launch that reads a list"},
+      {"quiet_col_group", "GOL_QUIET_COL_GROUP", "4", 'i', "tune",
+       "owned word columns per unit of the column kernel: 2, 4 or 8"},
+      {"quiet_col_items", "GOL_QUIET_COL_ITEMS", "42", 'i', "tune",
+       "quiet_cols auto: the longest reported candidate list the column kernel runs (42: where the short waves run)"},
       {"lazy_tail", "GOL_LAZY_TAIL", "-1", 'i', "tune",
        "a run whose last epoch is shorter than a block runs one full block instead and reports its limit; the "
        "generations beyond it carry into the next run, and a read of the grid rewinds and replays the remainder "

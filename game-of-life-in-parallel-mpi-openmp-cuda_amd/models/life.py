@@ -269,6 +269,11 @@ class Simulation:
                 # finished launch listed for its successor (-1: none reported yet).
                 "quiet_list": bool(self._eng.quiet_list),
                 "quiet_candidates": self._eng.quiet_candidates,
+                # The column kernel (tuning quiet_cols): on or off, and over its launches the word
+                # columns it computed against the owned word columns of the tiles it computed them in.
+                "quiet_cols": bool(self._eng.quiet_cols),
+                "quiet_cols_computed": self._eng.quiet_cols_counts()[0],
+                "quiet_cols_of_tiles": self._eng.quiet_cols_counts()[1],
                 # Lazy tail (tuning lazy_tail): the generation the block chain has reached (up to
                 # tmax - 1 past `generation` after a run that ended on a full block), runs that
                 # ended that way, and how many of those blocks a read of the grid had to replay.
