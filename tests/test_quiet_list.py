@@ -77,7 +77,20 @@ def test_flag_counts_pack_and_unpack():
     assert C.quiet_flag_delta(0x5, 0x5 | C.QUIET_DIRTY, 0) == 0  # detection bits are no flags
 
 
-@pytest.mark.parametrize("ncolw,nseg", [(3, 8), (1, 4), (2, 2)])
+def test_neighbourhoods_of_the_smallest_tori_repeat_tiles():
+    """One strip: a tile is its own left and right neighbour; one group: its own upper and lower one; two:
+    both neighbours are the same tile.  A computing tile then marks a tile several times (the stamps)."""
+    assert neighbours(0, 1, 1) == [0] * 9
+    assert neighbours(0, 1, 2) == [1, 1, 1, 0, 0, 0, 1, 1, 1] and neighbours(1, 1, 2) == [0, 0, 0, 1, 1, 1, 0, 0, 0]
+    assert neighbours(0, 2, 1) == [1, 0, 1] * 3 and neighbours(1, 2, 1) == [0, 1, 0] * 3
+    assert neighbours(0, 2, 2) == [3, 1, 3, 2, 0, 2, 3, 1, 3]
+    for ncolw, nseg in ((1, 1), (1, 2), (2, 1)):
+        for t in range(ncolw * nseg):
+            for n in set(neighbours(t, ncolw, nseg)):
+                assert t in neighbours(n, ncolw, nseg), (ncolw, nseg, t, n)
+
+
+@pytest.mark.parametrize("ncolw,nseg", [(3, 8), (1, 4), (2, 2), (1, 1), (1, 2), (2, 1)])
 @pytest.mark.parametrize("p_dirty", [0.15, 0.4])
 def test_list_computes_what_full_evaluation_computes(ncolw, nseg, p_dirty):
     tiles = ncolw * nseg
@@ -88,7 +101,10 @@ def test_list_computes_what_full_evaluation_computes(ncolw, nseg, p_dirty):
     for block in range(50):
         follow = prev is not None and block not in (10, 20, 21, 35, 42)  # invalidations, two in a row
         # Activity dies down in the middle of the chain, so lists get short and tiles leave them.
-        fresh = random_words(rng, tiles, p_dirty if block % 10 < 6 else 0.0)
+        p = p_dirty if block % 10 < 6 else 0.0
+        if tiles <= 2 and not follow:
+            p = 1.0  # one or two tiles: a clean first word would be republished until the next invalidation
+        fresh = random_words(rng, tiles, p)
         if follow:
             skip = [C.quiet_may_skip([prev[n] for n in neighbours(t, ncolw, nseg)]) for t in range(tiles)]
         else:
