@@ -158,8 +158,8 @@ class Backend {
     bool link = false;  // consecutive blocks may run linked (BlockArgs::link)
   };
   virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req,
-                                     Rule /*rule*/ = Rule{}) const {
-    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l)};
+                                     Rule /*rule*/ = Rule{}, Boundary boundary = Boundary::Torus) const {
+    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && boundary == Boundary::Torus};
   }
   // Quiet-tile skipping (BlockArgs::quiet, gol/quiet.hpp).  quiet_mode(): the
   // backend's tuning quiet_skip (0: it has no such kernel or it is off, 1
@@ -203,6 +203,16 @@ class Backend {
   virtual std::string unsupported_rule(Layout, Rule rule) const {
     return "backend " + name() + " does not run rule " + rule_string(rule);
   }
+  // Whether run_block honours BlockArgs::plane (the bounded plane) on tiles of
+  // this layout with `rule`; unsupported_boundary() is the message of the
+  // engine's refusal and names the combination.
+  virtual bool supports_boundary(Layout, Rule, Boundary b) const { return b == Boundary::Torus; }
+  virtual std::string unsupported_boundary(Layout, Rule, Boundary b) const {
+    return "backend " + name() + " does not run boundary=" + boundary_name(b);
+  }
+  // Description of the kernels that run the bounded plane ("" where the
+  // backend has one kind only).
+  virtual std::string plane_kernel(Layout) const { return ""; }
   // Row ring (single-rank torus): a tile whose top Dv halo rows are a second
   // virtual mapping of its last Dv owned rows and whose bottom halo rows map
   // its first ones, so the periodic row halos are always valid and never

@@ -39,6 +39,10 @@ struct CheckpointMeta {
   // it is not B3/S23 (checkpoints of the default rule are unchanged byte for
   // byte); a missing key means B3/S23.
   std::string rule = "B3/S23";
+  // "torus" or "dead" (EngineConfig::boundary).  As for the rule, meta.json
+  // carries a "boundary" key only when it is not the torus; a missing key
+  // means the torus.
+  std::string boundary = "torus";
   std::string grid = "grid.txt";  // grid file name inside the checkpoint directory
 };
 

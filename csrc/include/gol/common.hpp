@@ -27,6 +27,13 @@ enum class Layout : int { U8 = 0, Bits = 1 };
 
 inline const char* layout_name(Layout l) { return l == Layout::Bits ? "bits" : "u8"; }
 
+// What lies beyond the grid's edge.  Torus: the grid wraps (the reference's
+// only world, and the default).  Dead: the bounded plane - cells outside
+// [0, W) x [0, H) are dead in every generation.
+enum class Boundary : int { Torus = 0, Dead = 1 };
+
+inline const char* boundary_name(Boundary b) { return b == Boundary::Dead ? "dead" : "torus"; }
+
 // Fail-stop error (the reference calls perror_exit / cudaSafeCall and exits:
 // src/game.c:19-23, src/game_cuda.cu:18-27).  We throw so that Python callers
 // get a RuntimeError; the CLI catches, prints and exits non-zero.
@@ -35,6 +42,12 @@ struct Error : std::runtime_error {
 };
 
 [[noreturn]] void fail(const std::string& msg);
+
+inline Boundary parse_boundary(const std::string& s) {
+  if (s == "torus") return Boundary::Torus;
+  if (s == "dead") return Boundary::Dead;
+  fail("bad boundary '" + s + "' (want torus or dead)");
+}
 
 #define GOL_REQUIRE(cond, msg)                                                  \
   do {                                                                          \

@@ -23,7 +23,10 @@ struct RefResult {
 // reference's OpenMP build (src/game_openmp.c:34).  `rule`: any Life-like
 // rule without B0, applied by its plain per-cell definition (the reference
 // itself is B3/S23 only): the exact oracle for "Generations" under any rule.
+// `boundary`: Boundary::Dead counts neighbours outside the grid as dead (the
+// bounded plane) instead of wrapping around the torus.
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
-                            bool check_similarity, int sim_freq, int threads, Rule rule = Rule{});
+                            bool check_similarity, int sim_freq, int threads, Rule rule = Rule{},
+                            Boundary boundary = Boundary::Torus);
 
 }  // namespace gol

@@ -43,6 +43,9 @@ struct Decomposition {
   Extent rows(int rank) const;        // global row range of a rank's tile
   Extent cols(int rank) const;        // global column (cell) range
   std::array<int, 8> neighbors(int rank) const;  // indexed by Dir
+  // plane: the bounded plane's form - no wrap, -1 where the rank's side (or
+  // corner) lies on the grid's edge and so has no partner.
+  std::array<int, 8> neighbors(int rank, bool plane) const;
 
   // "auto" -> 1 x P row strips (contiguous halos); "PxQ" -> Px=P, Py=Q.
   static Decomposition make(int64_t W, int64_t H, int nranks, const std::string& spec,

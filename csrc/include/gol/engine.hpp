@@ -32,6 +32,13 @@ struct EngineConfig {
   int64_t W = 0, H = 0;            // global grid (cells)
   Layout layout = Layout::Bits;
   Rule rule;                       // Life-like rule (common.hpp), default B3/S23; no B0
+  // Torus (default) or the bounded plane, whose outside is dead in every
+  // generation.  On the plane the edge is enforced inside the temporal blocks
+  // (BlockArgs::plane), and everything that relies on the wrap is off: no row
+  // ring, no wrapped rows or columns, no drifting frame, no folded strip, no
+  // linked or chained launches, no quiet-tile skipping, no lazy tail, no
+  // periodic fills; ranks exchange halos only across edges between ranks.
+  Boundary boundary = Boundary::Torus;
   std::string decomp = "auto";     // "auto" or "PxQ"
   int64_t gen_limit = 1000;        // GEN_LIMIT (src/game.c:6)
   bool check_similarity = true;    // CHECK_SIMILARITY (src/game.c:8)
@@ -367,7 +374,9 @@ class Engine {
   // Phase-timed Backend::fill_periodic on the compute stream.
   void fill(void* buf, const TileGeom& g, bool cols, bool rows);
   void exchange_columns(void* buf, const TileGeom& g);
+  // Without the operations whose peer is -1 (a side on the plane's edge).
   std::vector<P2POp> row_ops(void* buf, const TileGeom& g) const;
+  std::array<int, 8> neighbors() const { return dec_.neighbors(rank_, plane_); }
   void halo_exchange_on(void* buf, const TileGeom& g);
   // Byte layout on bit words (EngineConfig::u8_compute = 1): the per-run
   // pack / unpack of the byte tile; the epochs run on compute_tile().
@@ -432,6 +441,7 @@ class Engine {
   double watchdog_s_ = 900;
   int64_t gen_ = 0;
   int64_t exchanges_ = 0, polls_ = 0, launches_ = 0;
+  bool plane_ = false;      // EngineConfig::boundary == Boundary::Dead
   bool drift_ok_ = false;   // whole-width tile of 32-cell words on a drifting backend
   bool cols_filled_ = true; // column halos kept valid by fills (false: the backend wraps column reads)
   bool rows_wrapped_ = false; // single-rank torus read modulo its rows (no fills at all)

@@ -111,6 +111,15 @@ struct BlockArgs {
   // light cone are what they were T generations ago.  Results are the same
   // either way; a backend without such a kernel ignores it.
   bool quiet = false;
+  // Bounded plane (EngineConfig::boundary == Boundary::Dead): the padded rows
+  // [grid_row_lo, grid_row_hi) and padded cells [grid_cell_lo, grid_cell_hi)
+  // are inside the grid; every cell outside them is dead in every generation
+  // of the block, whatever the input holds there, and is written as dead.  A
+  // side of the tile that borders another rank's tile passes the tile's own
+  // bound (0, R(), 32 Wp()).  grid_cell_lo is a multiple of 32.  Never set
+  // together with allow_drift, wrap_rows, full_width, link, ring or quiet.
+  bool plane = false;
+  int64_t grid_row_lo = 0, grid_row_hi = 0, grid_cell_lo = 0, grid_cell_hi = 0;
 };
 
 }  // namespace gol

@@ -67,6 +67,13 @@ std::string life_block_variant(Layout layout, const LifeTuning& tune) {
          (grouped && tune.chain == 1 ? " chain" : grouped && tune.chain < 0 ? " chain=tuned" : "");
 }
 
+std::string life_block_plane_variant(Layout layout, const LifeTuning& tune) {
+  const bool grouped = tune.group != 0;
+  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp plane" +
+         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window on the plane)" : "") +
+         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "");
+}
+
 int life_block_max_T(Layout layout, const LifeTuning& tune) {
   if (layout == Layout::U8 && tune.u8_lds) return tune.lds_T;
   // Register budget for 2 waves/SIMD (<= 256 VGPRs): T <= 16 (one word per lane).
@@ -110,6 +117,31 @@ LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const
   p.link_ring_rows = a.ring && a.row_lo == g.Dv && a.row_hi == g.Dv + g.H ? g.H : 0;
   p.fault_delay = tune.fault_delay;
   const int64_t rows = a.row_hi - a.row_lo;
+  if (a.plane) {
+    // The bounded plane: lb::PlaneIO kernels, B3/S23 on the DPP window (a
+    // forced adder window runs the DPP window too: its drifting frame is a
+    // relabelling of torus columns).  The engine refuses the combinations that
+    // have no plane kernel before any launch; these guard the launcher itself.
+    GOL_REQUIRE(rule_is_default(a.rule), "life_block: boundary=dead runs B3/S23 only on the HIP engine");
+    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: boundary=dead with u8_kernel=lds");
+    GOL_REQUIRE(!a.allow_drift && !a.full_width && !a.wrap_rows && !a.ring && !a.link && !a.quiet,
+                "life_block: boundary=dead with a torus-only launch option");
+    GOL_REQUIRE(a.T <= 16, "life_block: plane kernels run temporal blocks of at most 16 generations");
+    GOL_REQUIRE(g.R() < (int64_t(1) << 30), "life_block: boundary=dead needs fewer than 2^30 tile rows");
+    GOL_REQUIRE(a.grid_row_lo >= 0 && a.grid_row_lo < a.grid_row_hi && a.grid_row_hi <= g.R() &&
+                    a.grid_cell_lo >= 0 && a.grid_cell_lo % 32 == 0 && a.grid_cell_lo < a.grid_cell_hi &&
+                    a.grid_cell_hi <= 32 * g.Wp(),
+                "life_block: grid bounds outside the tile");
+    p.wrap_w = 0;
+    p.link_ring_rows = 0;
+    p.grid_row_lo = int(a.grid_row_lo);
+    p.grid_row_hi = int(a.grid_row_hi);
+    p.grid_w0 = int(a.grid_cell_lo / 32);
+    p.grid_w1 = int(ceil_div(a.grid_cell_hi, 32));
+    const int64_t gtail = a.grid_cell_hi % 32;
+    p.grid_last_mask = gtail ? (0xFFFFFFFFu >> (32 - gtail)) : 0xFFFFFFFFu;
+    return (g.layout == Layout::U8 ? launch_plane_u8_dpp : launch_plane_bits_dpp)(p, rows, a.T, tune, ctx, stream);
+  }
   int x = tune.xlane == kXlaneAdd || tune.xlane == kXlaneAuto ? tune.xlane : kXlaneDpp;
   // Any rule but B3/S23: the kernels compiled from life_rules.def.
   const RuleKernels* rk = nullptr;

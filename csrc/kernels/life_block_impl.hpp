@@ -101,6 +101,34 @@ __device__ __forceinline__ bool wave_halo(int lane, int i) {
   }
 }
 
+// ---- edge policies (the IO policies' Edge member) ----------------------------
+// Torus: the grid wraps; the kernels know nothing of its edge (no code).
+// Plane: the bounded plane (EngineConfig::boundary == dead).  Cells outside
+// the grid are dead in every generation, also inside a temporal block and deep
+// in a halo, so every input row as it is converted and every level row
+// level_full produces is ANDed with "inside the grid": a wave-uniform row test
+// in SGPRs (one unsigned 32-bit compare of the row against the grid's row
+// count) and one constant column mask per lane word, combined in a single
+// v_bitop3 (AND3) per level body.  Outputs are masked, so the halo rows and
+// words a block writes are zero; inputs are masked, so nothing ever has to
+// fill the grid's outer edge: its rows and words only have to be addressable.
+struct Torus {
+  static constexpr bool kPlane = false;
+};
+struct Plane {
+  static constexpr bool kPlane = true;
+};
+template <class Edge, int W>
+struct EdgeState {};
+template <int W>
+struct EdgeState<Plane, W> {
+  uint32_t cm[W];  // in-grid cells of the lane's word i (LifeBlockParams::grid_w0 / grid_w1 / grid_last_mask)
+  int rel;         // the wave's first input row (sweep step 0) minus LifeBlockParams::grid_row_lo
+  uint32_t rows;   // grid_row_hi - grid_row_lo
+  // All ones if the level-L row of sweep step k lies inside the grid (wave-uniform).
+  __device__ __forceinline__ uint32_t row_mask(int k, int L) const { return uint32_t(rel + k - L) < rows ? ~0u : 0u; }
+};
+
 // Column map of one lane (all life_block kernels).
 //   Halo mode (p.wrap_w == 0): the lane's words are padded-row words
 //   kcol * kWaveOut - 1 + W * lane + i; the engine keeps the halo columns
@@ -163,6 +191,24 @@ __device__ __forceinline__ LaneCols<IO> lane_cols(const LifeBlockParams& p, int 
     c.off[i] = p.own_w0 + ((lc % ww) + ww) % ww;
   }
   return c;
+}
+
+// Plane: the lane's column masks and the wave's row origin (in0: the padded
+// row of sweep step 0).  Plane launches run in halo mode (never wrap), so the
+// lane's word i is padded word store_col + i.  Rows in 32 bits: the launcher
+// checks that the tile has fewer than 2^31 rows.
+template <class IO>
+__device__ __forceinline__ void edge_init(EdgeState<typename IO::Edge, IO::W>& e, const LifeBlockParams& p,
+                                          const LaneCols<IO>& lc, int64_t in0) {
+  if constexpr (IO::Edge::kPlane) {
+#pragma unroll
+    for (int i = 0; i < IO::W; ++i) {
+      const int cc = lc.store_col + i;
+      e.cm[i] = (cc >= p.grid_w0 && cc < p.grid_w1) ? (cc == p.grid_w1 - 1 ? p.grid_last_mask : ~0u) : 0u;
+    }
+    e.rel = int(in0) - p.grid_row_lo;
+    e.rows = uint32_t(p.grid_row_hi - p.grid_row_lo);
+  }
 }
 
 // One-sided window for the adder mode: l1 = cells x-1, l2 = cells x-2 at bit
@@ -319,6 +365,7 @@ struct LifeLike {
 template <int W_, int XL_, class Rule_ = Conway>
 struct BitsIO {
   using Rule = Rule_;
+  using Edge = Torus;  // PlaneIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = 1;  // halo lanes per wave side
   static constexpr bool kLinked = false;  // Sc1IO
@@ -361,6 +408,7 @@ struct BitsIO {
 template <int W_, int XL_, int HALO_ = 1, class Rule_ = Conway>
 struct U8IO {
   using Rule = Rule_;
+  using Edge = Torus;  // PlaneIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = HALO_;  // halo lanes per wave side (2: passes deeper than 32)
   static constexpr bool kLinked = false;  // Sc1IO
@@ -445,6 +493,13 @@ struct Sc1IO : IO {
   }
 };
 
+// Storage layout of a bounded-plane launch: IO with the Plane edge policy (a
+// wrapper like Sc1IO, so the torus instantiations keep their names).
+template <class IO>
+struct PlaneIO : IO {
+  using Edge = Plane;
+};
+
 // Row reader with a 3-deep register prefetch: the row for step k sits in
 // slot k % 3 and is replaced by the load for step k + 3 when consumed.
 // Rows in flight per wave: sets of 3 (the window's slots), the oldest set
@@ -491,24 +546,42 @@ struct RowReader {
 
 // Per-wave state.  Level L (0..T-1) keeps, for its last three rows (slot =
 // row index mod 3), the horizontal sums h0/h1 and the cells themselves.
-template <int T, int W>
+template <int T, int W, class Edge = Torus>
 struct Levels {
   Vec<W> h0[T][3], h1[T][3], cc[T][3];
   Vec<W> acc[T];  // per word: OR of (new ^ old) per produced level L+1
+  EdgeState<Edge, W> edge;
 };
+template <int T, class IO>
+using LevelsOf = Levels<T, IO::W, typename IO::Edge>;
+
+// Plane: the input row of sweep step k, cells outside the grid cleared.
+template <class IO, class St, int W = IO::W>
+__device__ __forceinline__ Vec<W> edge_input(const St& st, Vec<W> cur, int k) {
+  if constexpr (IO::Edge::kPlane) {
+    const uint32_t rm = st.edge.row_mask(k, 0);
+#pragma unroll
+    for (int i = 0; i < W; ++i) cur.w[i] = cur.w[i] & st.edge.cm[i] & rm;
+  }
+  return cur;
+}
 
 // Level L at a step in slot S: push the new level-L row `cur` into the
-// window and produce the level-(L+1) row one row above it.
+// window and produce the level-(L+1) row one row above it.  k: the sweep
+// step (the level-L row is the wave's first input row + k - L), which only the
+// Plane edge policy looks at.
 template <int T, class IO, int S, int L, int W = IO::W>
-__device__ __forceinline__ Vec<W> level_full(Levels<T, W>& st, const Vec<W>& cur) {
+__device__ __forceinline__ Vec<W> level_full(LevelsOf<T, IO>& st, const Vec<W>& cur_in, int k = 0) {
   constexpr int s1 = (S + 1) % 3, s2 = (S + 2) % 3;
   Vec<W> h0, h1, nxt, c;
+  const Vec<W> cur = L == 0 ? edge_input<IO>(st, cur_in, k) : cur_in;
   hsum<IO::XL>(cur, h0, h1, c);
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     const uint32_t ctr = st.cc[L][s2].w[i];
     nxt.w[i] = IO::Rule::eval(st.h0[L][s1].w[i], st.h1[L][s1].w[i], st.h0[L][s2].w[i], st.h1[L][s2].w[i], h0.w[i],
                               h1.w[i], ctr);
+    if constexpr (IO::Edge::kPlane) nxt.w[i] = bop3<tt::AND3>(nxt.w[i], st.edge.cm[i], st.edge.row_mask(k, L + 1));
     st.acc[L].w[i] = bop3<tt::OR_XOR>(st.acc[L].w[i], nxt.w[i], ctr);
     // Opaque def: in straight-line code (prologue / grouped epilogue) hipcc
     // otherwise reassociates the flag ORs of many steps into one late tree
@@ -523,8 +596,9 @@ __device__ __forceinline__ Vec<W> level_full(Levels<T, W>& st, const Vec<W>& cur
 
 // Window fill only (the level's output row would still be invalid).
 template <int T, class IO, int S, int L, int W = IO::W>
-__device__ __forceinline__ void level_store(Levels<T, W>& st, const Vec<W>& cur) {
+__device__ __forceinline__ void level_store(LevelsOf<T, IO>& st, const Vec<W>& cur_in, int k = 0) {
   Vec<W> h0, h1, c;
+  const Vec<W> cur = L == 0 ? edge_input<IO>(st, cur_in, k) : cur_in;
   hsum<IO::XL>(cur, h0, h1, c);
   st.h0[L][S] = h0;
   st.h1[L][S] = h1;
@@ -532,9 +606,9 @@ __device__ __forceinline__ void level_store(Levels<T, W>& st, const Vec<W>& cur)
 }
 
 template <int T, class IO, int S, int L, int LEND, int W = IO::W>
-__device__ __forceinline__ Vec<W> levels_full(Levels<T, W>& st, const Vec<W>& cur) {
+__device__ __forceinline__ Vec<W> levels_full(LevelsOf<T, IO>& st, const Vec<W>& cur, int k = 0) {
   if constexpr (L < LEND) {
-    return levels_full<T, IO, S, L + 1, LEND>(st, level_full<T, IO, S, L>(st, cur));
+    return levels_full<T, IO, S, L + 1, LEND>(st, level_full<T, IO, S, L>(st, cur, k), k);
   } else {
     return cur;
   }
@@ -545,15 +619,15 @@ __device__ __forceinline__ Vec<W> levels_full(Levels<T, W>& st, const Vec<W>& cu
 // window.
 // RD: RowReader<IO>, or any source with take<S>(k).
 template <int T, class IO, int K, class Save, class Bottom, class RD>
-__device__ __forceinline__ void prologue_tri(Levels<T, IO::W>& st, RD& rd, const Save& save, const Bottom& bottom) {
+__device__ __forceinline__ void prologue_tri(LevelsOf<T, IO>& st, RD& rd, const Save& save, const Bottom& bottom) {
   if constexpr (K < 2 * T) {
     constexpr int S = K % 3;
     constexpr int nfull = K / 2;
-    const Vec<IO::W> cur = levels_full<T, IO, S, 0, nfull>(st, rd.template take<S>(K));
+    const Vec<IO::W> cur = levels_full<T, IO, S, 0, nfull>(st, rd.template take<S>(K), K);
     // Level `nfull` rows in0 + nfull (K even) and in0 + nfull + 1 (K odd):
     // the grouped kernel shares them with the wave above (life_group_impl.hpp).
     if constexpr (nfull >= 1 && nfull < T) save(nfull, K - 2 * nfull, cur);
-    if constexpr (nfull < T) level_store<T, IO, S, nfull>(st, cur);
+    if constexpr (nfull < T) level_store<T, IO, S, nfull>(st, cur, K);
     prologue_tri<T, IO, K + 1>(st, rd, save, bottom);
   }
 }
@@ -637,7 +711,7 @@ void life_block_kernel(const LifeBlockParams p) {
     fmask[i] = lc.fmask[i];
   }
 
-  Levels<T, W> st;
+  LevelsOf<T, IO> st;
 #pragma unroll
   for (int L = 0; L < T; ++L) {
 #pragma unroll
@@ -647,6 +721,7 @@ void life_block_kernel(const LifeBlockParams p) {
       st.acc[L].w[i] = 0u;
     }
   }
+  edge_init<IO>(st.edge, p, lc, o0 - T);
 
   constexpr int kPro = 2 * T;
   const int kend = kPro + int(o1 - o0);
@@ -665,13 +740,13 @@ void life_block_kernel(const LifeBlockParams p) {
   int k = kPro;
   constexpr int S0 = kPro % 3, S1 = (S0 + 1) % 3, S2 = (S0 + 2) % 3;
   for (; k + 3 <= kend; k += 3) {
-    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k)));
-    wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1)));
-    wr.row(k + 2 - T, levels_full<T, IO, S2, 0, T>(st, rd.template take<S2>(k + 2)));
+    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k), k));
+    wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1), k + 1));
+    wr.row(k + 2 - T, levels_full<T, IO, S2, 0, T>(st, rd.template take<S2>(k + 2), k + 2));
   }
   if (k < kend) {
-    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k)));
-    if (k + 1 < kend) wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1)));
+    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k), k));
+    if (k + 1 < kend) wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1), k + 1));
   }
 
   // Fused termination flags: one bit per generation level, counting only

@@ -147,7 +147,7 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
   // tiles, whose launches alone hold 2 waves per SIMD).  Any other launch
   // first joins the two streams.
   if (ctx.link) {
-    if constexpr (IO::Rule::kDefault && IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
+    if constexpr (IO::Rule::kDefault && !IO::Edge::kPlane && IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
                   (IO::XL == kXlaneDpp || IO::XL == kXlaneAdd)) {
       if (tune.group != 0) {
         // Blocks of T <= 8 link 4-wave groups where the unlinked path would
@@ -195,7 +195,8 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
       // strip's last.  Stream launches only (the flags count launches, so a
       // replayed graph would see its own stale flags).
       // Rule kernels (IO::Rule other than Conway) are never linked or chained.
-      if (IO::Rule::kDefault && ctx.chain) {
+      // Neither are the plane's kernels (lb::PlaneIO).
+      if (IO::Rule::kDefault && !IO::Edge::kPlane && ctx.chain) {
         LifeBlockParams ch = p;
         ch.fold = 1;
         ch.fold_lanes = 64;
@@ -266,11 +267,11 @@ LaunchResult launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, c
     case 16: return launch_T<16, IO>(p, out_rows, tune, ctx, s);
     case 24:  // byte layout only: fewer byte-grid passes per generation
       // (the adder window never runs T > 16: launch_life_block switches it to DPP)
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault)
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane)
         return launch_deep<24, IO>(p, out_rows, tune, ctx, s);
       [[fallthrough]];
     case 32:
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault) {
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane) {
         if (T == 32) return launch_deep<32, IO>(p, out_rows, tune, ctx, s);
       }
       [[fallthrough]];
@@ -311,3 +312,18 @@ namespace rules {
 #define GOL_RULE_TU_BITS_DPP(name) GOL_RULE_TU(name, bits_dpp, GOL_RULE_IO_BITS, kXlaneDpp)
 #define GOL_RULE_TU_BITS_ADD(name) GOL_RULE_TU(name, bits_add, GOL_RULE_IO_BITS, kXlaneAdd)
 #define GOL_RULE_TU_U8_DPP(name) GOL_RULE_TU(name, u8_dpp, GOL_RULE_IO_U8, kXlaneDpp)
+
+// Bounded-plane kernels (lb::PlaneIO): B3/S23, the DPP window, in the T and
+// classic / grouped variants of a rule translation unit;
+// life_block_plane_<variant>.hip, each one line:
+//   GOL_PLANE_TU_BITS_DPP | GOL_PLANE_TU_U8_DPP
+#define GOL_PLANE_TU(variant, IO_)                                                       \
+  namespace gol {                                                                        \
+  namespace hipk {                                                                       \
+  GOL_LIFE_VARIANT(launch_plane_##variant) {                                             \
+    return lb::launch_variant<lb::PlaneIO<IO_>>(p, out_rows, T, tune, ctx, s);           \
+  }                                                                                      \
+  }                                                                                      \
+  }
+#define GOL_PLANE_TU_BITS_DPP GOL_PLANE_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
+#define GOL_PLANE_TU_U8_DPP GOL_PLANE_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))

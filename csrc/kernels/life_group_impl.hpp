@@ -267,7 +267,7 @@ struct Prio {
 // branch beside the epilogue made hipcc allocate 199 instead of 123 VGPRs.
 // WR: Writer<IO>, or any sink with row(r, v) (life_quiet_impl.hpp).
 template <int T, class IO, int E, int S, class WR>
-__device__ __forceinline__ void epilogue_tri(Levels<T, IO::W>& st, RowReader<IO>& rd, const uint32_t* below,
+__device__ __forceinline__ void epilogue_tri(LevelsOf<T, IO>& st, RowReader<IO>& rd, const uint32_t* below,
                                              int lane, WR& wr, int k, int nfull, Prio& prio) {
   if constexpr (E < 2 * T) {
     if (E >= nfull) return;  // wave-uniform
@@ -281,7 +281,7 @@ __device__ __forceinline__ void epilogue_tri(Levels<T, IO::W>& st, RowReader<IO>
 #pragma unroll
       for (int i = 0; i < W; ++i) cur.w[i] = below[(((L0 - 1) * 2 + (E & 1)) * W + i) * 64 + lane];
     }
-    wr.row(k - T, levels_full<T, IO, S, L0, T>(st, cur));
+    wr.row(k - T, levels_full<T, IO, S, L0, T>(st, cur, k));
     // Keep the scheduler inside one step: interleaving the whole epilogue
     // (272 level bodies at T = 16) blows the register budget.
     if constexpr (E % GOL_EPI_SCHED == GOL_EPI_SCHED - 1) __builtin_amdgcn_sched_barrier(0);
@@ -346,8 +346,8 @@ void life_group_kernel(const LifeBlockParams p) {
   // recomputes its upper neighbour's last row, identically), so the wave's
   // control flow is the same for all of them; lanes carry their group's row
   // offset in their read / store offsets.
-  // fold == 1 (launch_T); rule kernels are never chained (the wait compiles out)
-  const bool chain = IO::Rule::kDefault && p.chain_buf != nullptr;
+  // fold == 1 (launch_T); rule and plane kernels are never chained (the wait compiles out)
+  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && p.chain_buf != nullptr;
   int kcol, grp, nsub = 1, sub_lanes = 64;
   if (p.fold > 1 && blk >= (p.ncolw - 1) * p.nseg) {
     kcol = p.ncolw - 1;
@@ -409,7 +409,7 @@ void life_group_kernel(const LifeBlockParams p) {
     fmask[i] = lc.fmask[i];
   }
 
-  Levels<T, W> st;
+  LevelsOf<T, IO> st;
 #pragma unroll
   for (int L = 0; L < T; ++L) {
 #pragma unroll
@@ -419,6 +419,7 @@ void life_group_kernel(const LifeBlockParams p) {
       st.acc[L].w[i] = 0u;
     }
   }
+  edge_init<IO>(st.edge, p, lc, in0);
 
   if constexpr (IO::kLinked) {  // wait for the previous launch's rows this group reads
     // (a folded block: the rows of all its groups)
@@ -460,9 +461,9 @@ void life_group_kernel(const LifeBlockParams p) {
   Prio prio((kmain - kPro) * T + epi_work<T>(nfull), hot);
   for (; k + 3 <= kmain; k += 3) {
     prio.at((k - kPro) * T);
-    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k)));
-    wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1)));
-    wr.row(k + 2 - T, levels_full<T, IO, S2, 0, T>(st, rd.template take<S2>(k + 2)));
+    wr.row(k - T, levels_full<T, IO, S0, 0, T>(st, rd.template take<S0>(k), k));
+    wr.row(k + 1 - T, levels_full<T, IO, S1, 0, T>(st, rd.template take<S1>(k + 1), k + 1));
+    wr.row(k + 2 - T, levels_full<T, IO, S2, 0, T>(st, rd.template take<S2>(k + 2), k + 2));
   }
 
   prio.done0 = (kmain - kPro) * T;

@@ -131,6 +131,15 @@ struct LifeBlockParams {
   const uint32_t* quiet_rec_prev;
   uint32_t* quiet_rec_next;
   int quiet_bands;
+  // Bounded plane (BlockArgs::plane; the kernels of lb::PlaneIO): the padded
+  // rows [grid_row_lo, grid_row_hi) and padded words [grid_w0, grid_w1) that
+  // lie inside the grid, and the in-grid cells of word grid_w1 - 1.  A side of
+  // the tile that is not the grid's edge passes the tile's own bound, which
+  // masks nothing.  Rows in 32 bits, as for bnd_g (SGPR budget).  Unused by
+  // every other kernel.
+  int grid_row_lo, grid_row_hi;
+  int grid_w0, grid_w1;
+  uint32_t grid_last_mask;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -334,6 +343,8 @@ std::vector<Rule> life_block_rules();
 bool life_block_has_rule(Rule r);
 // Description of the kernel variant the tuning selects for a layout.
 std::string life_block_variant(Layout layout, const LifeTuning& tune);
+// The same for a bounded-plane engine (BlockArgs::plane).
+std::string life_block_plane_variant(Layout layout, const LifeTuning& tune);
 // Largest T that keeps 2 waves/SIMD for the variant's words-per-lane.
 int life_block_max_T(Layout layout, const LifeTuning& tune);
 
@@ -345,6 +356,10 @@ GOL_LIFE_VARIANT(launch_bits_w1_dpp);
 GOL_LIFE_VARIANT(launch_u8_w1_dpp);
 GOL_LIFE_VARIANT(launch_bits_w1_add);
 GOL_LIFE_VARIANT(launch_u8_w1_add);
+// The bounded plane (lb::PlaneIO; life_block_plane_*.hip): DPP window only -
+// the adder window's drifting frame is a relabelling of torus columns.
+GOL_LIFE_VARIANT(launch_plane_bits_dpp);
+GOL_LIFE_VARIANT(launch_plane_u8_dpp);
 // The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave
 // groups of short segments; life_block_bits_w1_dpp_quiet.hip): wrap-mode
 // blocks over a row ring's owned rows only.  Returns the tiles launched, 0

@@ -150,7 +150,7 @@ class CpuBackend final : public Backend {
   // three times (last owned rows, the owned rows, first owned rows), so the
   // engine's ring schedule is testable on the CPU.
   int row_ring_halo(int64_t H, int64_t pitch, int min_halo) const override {
-    if (!ring_) return 0;
+    if (!ring_) return 0;  // (the engine asks for no ring on the bounded plane)
     const int64_t page = ::sysconf(_SC_PAGESIZE);
     int64_t dv = std::max<int64_t>(1, min_halo);
     while ((dv * pitch) % page != 0) ++dv;  // pitch is a multiple of 256
@@ -191,6 +191,8 @@ class CpuBackend final : public Backend {
   bool drifts(Layout) const override { return drift_; }
   // Any Life-like rule (B0 is refused by the engine itself).
   bool supports_rule(Layout, Rule) const override { return true; }
+  // The bounded plane with any rule (run_block masks every level row).
+  bool supports_boundary(Layout, Rule, Boundary) const override { return true; }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override;
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t r0,
                     int64_t n) override;
@@ -291,6 +293,23 @@ int CpuBackend::run_block(const BlockArgs& a) {
   // column x, so after T levels the row sits T cells to the right with zeros
   // (junk on the GPU) entering at the left edge of the padded row.
   const int drift = (drift_ && a.allow_drift && T < 32 && 32 * g.hw >= 2 * T) ? T : 0;
+  // Bounded plane (BlockArgs::plane), as the HIP plane kernels do it: every
+  // input row as it is read and every level row as it is produced is ANDed
+  // with "inside the grid" - a row test and one mask per padded word.
+  std::vector<uint32_t> inside;
+  if (a.plane) {
+    GOL_REQUIRE(!drift && !a.wrap_rows && !a.ring, "run_block: the bounded plane neither drifts nor wraps");
+    inside.resize(size_t(Wp));
+    for (int64_t c = 0; c < Wp; ++c) {
+      uint32_t m = 0;
+      for (int j = 0; j < 32; ++j) m |= uint32_t(32 * c + j >= a.grid_cell_lo && 32 * c + j < a.grid_cell_hi) << j;
+      inside[size_t(c)] = m;
+    }
+  }
+  const auto clip = [&](uint32_t* row, int64_t r) {  // row r of any level
+    const bool in_rows = r >= a.grid_row_lo && r < a.grid_row_hi;
+    for (int64_t c = 0; c < Wp; ++c) row[c] = in_rows ? row[c] & inside[size_t(c)] : 0u;
+  };
 
   // Row bands: each task runs all T levels of its output rows [lo, hi) on the
   // trapezoid [lo - T + L, hi + T - L) of level L, in private buffers (the
@@ -336,6 +355,7 @@ int CpuBackend::run_block(const BlockArgs& a) {
           std::memcpy(w, in + r * g.pitch, size_t(4 * Wp));
         else
           for (int64_t c = 0; c < Wp; ++c) w[c] = read_word(in, g, r, c);
+        if (a.plane) clip(w, r);
         hsum_row(w, Wp, hs0(0, s0), hs1(0, s0));
         ++cnt[0];
         for (int L = 0; L < T && cnt[size_t(L)] >= 3; ++L) {
@@ -348,6 +368,11 @@ int CpuBackend::run_block(const BlockArgs& a) {
                                               cells(L, sb), Wp, owned.data(), dst)
                                    : rule_row(a.rule, hs0(L, sa), hs1(L, sa), hs0(L, sb), hs1(L, sb), hs0(L, sc),
                                               hs1(L, sc), cells(L, sb), Wp, owned.data(), dst);
+          if (a.plane) {
+            // Level L + 1's row lo - T + L + n - 2.  The flags count owned
+            // cells only, which all lie inside the grid.
+            clip(dst, lo - T + L + n - 2);
+          }
           if (!last) {
             hsum_row(dst, Wp, hs0(L + 1, sd), hs1(L + 1, sd));
             ++cnt[size_t(L + 1)];

@@ -643,7 +643,8 @@ class HipBackend final : public Backend {
     const bool capturing = capturing_;  // capture_begin / capture_end (no query per launch)
     // Rule kernels (any rule but B3/S23) are never linked or chained, forced
     // link=1 / chain=1 included.
-    const bool conway = rule_is_default(a.rule);
+    // Nor are the plane's kernels (BlockArgs::plane), which never skip either.
+    const bool conway = rule_is_default(a.rule) && !a.plane;
     // Wave trace: launch trace_at_ (its `pair` form: and the next one).
     const int64_t traced = trace_at_ < 0 ? -1 : launches_ - trace_at_;
     const bool trace = traced == 0 || (traced == 1 && trace_pair_);
@@ -798,8 +799,17 @@ class HipBackend final : public Backend {
   // same window and T: their adder kernels keep four waves per SIMD at T = 12
   // (docs/PERFORMANCE.md "Life-like rules").  Their byte kernels stop at
   // T = 16, and they never link.
-  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule) const override {
-    KernelChoice k = choose_conway(l, rows, cols, tmax_req);
+  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule,
+                             Boundary boundary) const override {
+    // The bounded plane: the DPP window's choice of T (its kernels stop at
+    // T = 16 in both layouts), never drifting, never linked, never skipping.
+    if (boundary == Boundary::Dead) {
+      KernelChoice k = choose_conway(l, rows, cols, tmax_req, hipk::kXlaneDpp);
+      k.tmax = std::min(k.tmax, 16);
+      k.drift = k.link = false;
+      return k;
+    }
+    KernelChoice k = choose_conway(l, rows, cols, tmax_req, tune_.xlane);
     // quiet_skip=1: every block the skipping kernel's (the DPP window at its
     // block size, never linked); the auto policy keeps the choice above and
     // applies where that is blocks of the skipping kernel's size.
@@ -825,7 +835,19 @@ class HipBackend final : public Backend {
     return "rule " + rule_string(rule) + " is not compiled for the HIP engine (compiled: " + have +
            "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)";
   }
-  KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req) const {
+  bool supports_boundary(Layout l, Rule rule, Boundary b) const override {
+    return b == Boundary::Torus || (rule_is_default(rule) && !(l == Layout::U8 && tune_.u8_lds));
+  }
+  std::string unsupported_boundary(Layout l, Rule rule, Boundary b) const override {
+    if (l == Layout::U8 && tune_.u8_lds)
+      return std::string("boundary=") + boundary_name(b) +
+             " with u8_kernel=lds: the LDS-tiled byte kernels wrap their reads around the torus";
+    return std::string("boundary=") + boundary_name(b) + " with rule " + rule_string(rule) +
+           " on the HIP engine: the plane kernels are compiled for B3/S23 only (the cpu and ref engines run any "
+           "rule on the plane)";
+  }
+  std::string plane_kernel(Layout l) const override { return hipk::life_block_plane_variant(l, tune_); }
+  KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req, int xlane) const {
     KernelChoice k{tmax_req > 0 ? tmax_req : preferred_tmax(l), false};
     if (l == Layout::U8 && tmax_req <= 0 && !tune_.u8_lds) {
       const int64_t strips = ceil_div(cols + 32 * 16, 62 * 32);
@@ -836,10 +858,10 @@ class HipBackend final : public Backend {
           break;
         }
     }
-    if (tune_.xlane == hipk::kXlaneAdd && !(l == Layout::U8 && tune_.u8_lds)) {
+    if (xlane == hipk::kXlaneAdd && !(l == Layout::U8 && tune_.u8_lds)) {
       k.drift = true;
       if (tmax_req <= 0) k.tmax = 12;
-    } else if (tune_.xlane == hipk::kXlaneAuto && l == Layout::Bits && tune_.group != 0 &&
+    } else if (xlane == hipk::kXlaneAuto && l == Layout::Bits && tune_.group != 0 &&
                (tmax_req <= 0 || tmax_req == 12)) {
       constexpr int64_t kT = 12;
       const int64_t strips = ceil_div(ceil_div(cols, 32) + 16, 63);  // + a deep halo's words

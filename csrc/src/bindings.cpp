@@ -106,7 +106,8 @@ PYBIND11_MODULE(_gol, m) {
       .def("px_of", &Decomposition::px_of)
       .def("py_of", &Decomposition::py_of)
       .def("rank_of", &Decomposition::rank_of)
-      .def("neighbors", &Decomposition::neighbors)
+      .def("neighbors", [](const Decomposition& d, int rank, bool plane) { return d.neighbors(rank, plane); },
+           py::arg("rank"), py::arg("plane") = false)
       .def("describe", &Decomposition::describe);
   m.def("split_range", &split_range);
 
@@ -162,6 +163,10 @@ PYBIND11_MODULE(_gol, m) {
       .def("supports_rule", [](const Backend& b, Layout l, const std::string& rule) {
         return b.supports_rule(l, parse_rule(rule));
       })
+      .def("supports_boundary", [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary) {
+        return b.supports_boundary(l, parse_rule(rule), parse_boundary(boundary));
+      })
+      .def("plane_kernel", &Backend::plane_kernel)
       .def("bind_thread", &Backend::bind_thread);
   m.def("cpu_backend",
         [](int threads, int drift, std::optional<Tuning> tune) {
@@ -255,6 +260,8 @@ PYBIND11_MODULE(_gol, m) {
       .def_readwrite("layout", &EngineConfig::layout)
       .def_property("rule", [](const EngineConfig& c) { return rule_string(c.rule); },
                     [](EngineConfig& c, const std::string& s) { c.rule = parse_rule(s); })
+      .def_property("boundary", [](const EngineConfig& c) { return std::string(boundary_name(c.boundary)); },
+                    [](EngineConfig& c, const std::string& s) { c.boundary = parse_boundary(s); })
       .def_readwrite("decomp", &EngineConfig::decomp)
       .def_readwrite("gen_limit", &EngineConfig::gen_limit)
       .def_readwrite("check_similarity", &EngineConfig::check_similarity)
@@ -535,20 +542,22 @@ PYBIND11_MODULE(_gol, m) {
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",
         [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, int64_t gen_limit,
-           bool check_similarity, int sim_freq, int threads, const std::string& rule) {
+           bool check_similarity, int sim_freq, int threads, const std::string& rule, const std::string& boundary) {
           GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
           int64_t H = a.shape(0), W = a.shape(1);
           std::vector<uint8_t> g(a.data(), a.data() + W * H);
           const Rule rl = parse_rule(rule);
+          const Boundary bd = parse_boundary(boundary);
           RefResult r;
           {
             py::gil_scoped_release rel;
-            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl);
+            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl, bd);
           }
           return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W));
         },
         py::arg("grid"), py::arg("gen_limit") = 1000, py::arg("check_similarity") = true,
-        py::arg("sim_freq") = 3, py::arg("threads") = 1, py::arg("rule") = "B3/S23");
+        py::arg("sim_freq") = 3, py::arg("threads") = 1, py::arg("rule") = "B3/S23",
+        py::arg("boundary") = "torus");
 
   // ---- bitop3 / rule emulation (for kernel-level tests) ----
   m.def("rule_words", [](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2,

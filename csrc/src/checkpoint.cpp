@@ -134,6 +134,8 @@ void checkpoint_commit(const std::string& dir, const std::string& grid_path, Che
     << (m.check_similarity ? "true" : "false") << ",\n \"sim_freq\": " << m.sim_freq << ",\n \"layout\": \""
     << m.layout << "\",";
   if (!rule_is_default(parse_rule(m.rule))) o << "\n \"rule\": \"" << rule_string(parse_rule(m.rule)) << "\",";
+  if (parse_boundary(m.boundary) != Boundary::Torus)
+    o << "\n \"boundary\": \"" << boundary_name(parse_boundary(m.boundary)) << "\",";
   o << "\n \"grid\": \"" << m.grid << "\"\n}";
   const std::string tmp = dir + "/meta.json.tmp", fin = dir + "/meta.json";
   {
@@ -184,6 +186,8 @@ CheckpointMeta checkpoint_load(const std::string& dir) {
   if (!lay.empty()) m.layout = lay;
   const std::string rule = json_field(js, "rule");
   if (!rule.empty()) m.rule = rule_string(parse_rule(rule));
+  const std::string boundary = json_field(js, "boundary");
+  if (!boundary.empty()) m.boundary = boundary_name(parse_boundary(boundary));
   const std::string grid = json_field(js, "grid");
   if (!grid.empty()) {
     GOL_REQUIRE(checkpoint_grid_name_ok(grid), "checkpoint '" + dir + "': bad grid file name '" + grid +

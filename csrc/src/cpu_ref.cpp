@@ -1,5 +1,6 @@
 #include "gol/cpu_ref.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <memory>
 
@@ -9,7 +10,7 @@
 namespace gol {
 
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
-                            bool check_similarity, int sim_freq, int threads, Rule rule) {
+                            bool check_similarity, int sim_freq, int threads, Rule rule, Boundary boundary) {
   GOL_REQUIRE(int64_t(grid.size()) == W * H, "grid size mismatch");
   require_no_b0(rule, rule_string(rule));
   GOL_REQUIRE(sim_freq > 0, "similarity frequency must be positive");
@@ -42,18 +43,32 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
   while (!empty() && generation <= gen_limit) {
     const uint8_t* u = univ;
     uint8_t* n = next;
-    rows([&](int64_t rb, int64_t re) {
-      for (int64_t y = rb; y < re; ++y) {
-        const uint8_t* up = u + ((y + H - 1) % H) * W;
-        const uint8_t* mid = u + y * W;
-        const uint8_t* dn = u + ((y + 1) % H) * W;
-        for (int64_t x = 0; x < W; ++x) {
-          int64_t xl = x == 0 ? W - 1 : x - 1, xr = x == W - 1 ? 0 : x + 1;
-          int s = up[xl] + up[x] + up[xr] + mid[xl] + mid[xr] + dn[xl] + dn[x] + dn[xr];
-          n[y * W + x] = uint8_t(((mid[x] ? rule.survive : rule.birth) >> s) & 1u);
+    if (boundary == Boundary::Dead) {
+      // The bounded plane: a neighbour outside [0, W) x [0, H) is dead.
+      rows([&](int64_t rb, int64_t re) {
+        for (int64_t y = rb; y < re; ++y)
+          for (int64_t x = 0; x < W; ++x) {
+            int s = 0;
+            for (int64_t yy = std::max<int64_t>(0, y - 1); yy <= std::min(H - 1, y + 1); ++yy)
+              for (int64_t xx = std::max<int64_t>(0, x - 1); xx <= std::min(W - 1, x + 1); ++xx)
+                if (yy != y || xx != x) s += u[yy * W + xx];
+            n[y * W + x] = uint8_t(((u[y * W + x] ? rule.survive : rule.birth) >> s) & 1u);
+          }
+      });
+    } else {
+      rows([&](int64_t rb, int64_t re) {
+        for (int64_t y = rb; y < re; ++y) {
+          const uint8_t* up = u + ((y + H - 1) % H) * W;
+          const uint8_t* mid = u + y * W;
+          const uint8_t* dn = u + ((y + 1) % H) * W;
+          for (int64_t x = 0; x < W; ++x) {
+            int64_t xl = x == 0 ? W - 1 : x - 1, xr = x == W - 1 ? 0 : x + 1;
+            int s = up[xl] + up[x] + up[xr] + mid[xl] + mid[xr] + dn[xl] + dn[x] + dn[xr];
+            n[y * W + x] = uint8_t(((mid[x] ? rule.survive : rule.birth) >> s) & 1u);
+          }
         }
-      }
-    });
+      });
+    }
     if (check_similarity && ++counter == sim_freq) {
       if (similar()) break;
       counter = 0;

@@ -51,6 +51,16 @@ std::array<int, 8> Decomposition::neighbors(int rank) const {
   return n;
 }
 
+std::array<int, 8> Decomposition::neighbors(int rank, bool plane) const {
+  std::array<int, 8> n = neighbors(rank);
+  if (!plane) return n;
+  const int px = px_of(rank), py = py_of(rank);
+  static constexpr int dx[8] = {0, 0, -1, 1, -1, 1, -1, 1}, dy[8] = {-1, 1, 0, 0, -1, -1, 1, 1};  // by Dir
+  for (int d = 0; d < 8; ++d)
+    if (px + dx[d] < 0 || px + dx[d] >= Px || py + dy[d] < 0 || py + dy[d] >= Py) n[d] = -1;
+  return n;
+}
+
 Decomposition Decomposition::make(int64_t W, int64_t H, int nranks, const std::string& spec,
                                   int64_t col_unit) {
   GOL_REQUIRE(nranks > 0, "nranks must be positive");

@@ -39,6 +39,15 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   GOL_REQUIRE(cfg_.rule.birth < 512 && cfg_.rule.survive < 512, "rule: neighbour counts are 0..8");
   require_no_b0(cfg_.rule, rule_string(cfg_.rule));
   rank_ = tr_->rank();
+  plane_ = cfg_.boundary == Boundary::Dead;
+  if (plane_) {
+    // Combinations that exist on the torus only are refused, not run there.
+    GOL_REQUIRE(!cfg_.self_exchange,
+                "boundary=dead with self_exchange (--rehearse-rccl): the rehearsal sends a rank's rows to itself "
+                "around the torus, which the bounded plane does not have");
+    GOL_REQUIRE(cfg_.graphs <= 0,
+                "boundary=dead with graphs=1: captured epochs are not built for the bounded plane");
+  }
   if (cfg_.overlap == 1) cfg_.overlap = 3;  // "on" is the trigger schedule
   int64_t unit = (cfg_.layout == Layout::Bits || cfg_.W % 32 == 0) ? 32 : 1;
   if (cfg_.layout == Layout::Bits)
@@ -56,13 +65,16 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Layout the temporal blocks run on.
   const Layout cl = via_bits_ ? Layout::Bits : cfg_.layout;
+  if (plane_ && !be_->supports_boundary(cl, cfg_.rule, cfg_.boundary))
+    fail(be_->unsupported_boundary(cl, cfg_.rule, cfg_.boundary));
   if (!be_->supports_rule(cl, cfg_.rule)) fail(be_->unsupported_rule(cl, cfg_.rule));
   // Every rank must take the same decision (a drifting frame or a schedule
   // that moves a halo exchange is only consistent in lockstep), so it is
   // made for the smallest tile of the decomposition, not this rank's.
   const Backend::KernelChoice kc =
-      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule);
-  tmax_ = std::min(kc.tmax, cl == Layout::U8 ? 32 : 16);
+      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule,
+                         cfg_.boundary);
+  tmax_ = std::min(kc.tmax, cl == Layout::U8 && !plane_ ? 32 : 16);
   // Epoch depth: a deeper halo means fewer latency-bound exchanges (or local
   // periodic fills: two ~5 us launches each) but ~D redundant rows per epoch.
   // With the grouped kernel the per-rank tile costs the same from 8T to 24T
@@ -71,6 +83,9 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // each one latency-bound.
   const bool row_exchange = dec_.Py > 1 || cfg_.self_exchange;
   int D = cfg_.epoch > 0 ? cfg_.epoch : (tr_->size() > 1 || cfg_.self_exchange ? 16 : 8) * tmax_;
+  // A single rank on the plane has nothing to exchange or fill, so a deep
+  // halo would only add rows of dead cells to every block: one block per epoch.
+  if (plane_ && tr_->size() == 1 && cfg_.epoch <= 0) D = tmax_;
   if (dec_.Py > 1) D = int(std::min<int64_t>(D, min_tile_rows(dec_)));
   if (dec_.Px > 1) {
     int64_t cap = 32 * (min_tile_cols(dec_) / 32);
@@ -82,10 +97,13 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // A drifting kernel (one-sided window, Backend::drifts) consumes 2 cells of
   // left halo per generation and none on the right; it needs the tile to be
   // the whole torus width so that the drift is a relabeling of columns.
-  drift_ok_ = kc.drift && dec_.Px == 1 && cfg_.W % 32 == 0;
+  // Never on the plane: the drift is a relabelling of torus columns.
+  drift_ok_ = kc.drift && dec_.Px == 1 && cfg_.W % 32 == 0 && !plane_;
   // Whole-width tiles on a backend that wraps column reads (lane_cols in the
   // HIP kernels) never read their halo columns: no column fills.
-  cols_filled_ = !(dec_.Px == 1 && cfg_.W % 32 == 0 && be_->wraps_columns(cl));
+  // The plane never wraps: its tiles keep halo columns (so every lane has a
+  // word to address), which nothing fills - the kernels mask them.
+  cols_filled_ = plane_ || !(dec_.Px == 1 && cfg_.W % 32 == 0 && be_->wraps_columns(cl));
   // A single-rank torus on a backend that also wraps row reads (the LDS-tiled
   // byte kernels): one block per epoch over the owned rows, no fills at all.
   rows_wrapped_ = !cols_filled_ && dec_.Px == 1 && dec_.Py == 1 && !cfg_.self_exchange && be_->wraps_rows(cl);
@@ -103,7 +121,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // falls back to plain buffers with periodic fills.
   int ring_dv = 0;
   Owned<> ring_bufs[2];
-  if (dec_.Px == 1 && dec_.Py == 1 && !cfg_.self_exchange && !rows_wrapped_) {
+  if (dec_.Px == 1 && dec_.Py == 1 && !cfg_.self_exchange && !rows_wrapped_ && !plane_) {
     const TileGeom probe = TileGeom::make(cl, r.size(), c.size(), 0, hw);
     ring_dv = be_->row_ring_halo(probe.H, probe.pitch, tmax_);
     // The byte layout on bit words keeps its byte tiles too: the rings must
@@ -146,7 +164,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // Linked launches (Backend::KernelChoice::link): consecutive blocks of an
   // epoch overlap; anything else on the stream (fills, exchanges, polls)
   // joins the streams first.  Not with column fills between blocks.
-  link_ = kc.link && !cols_filled_;
+  link_ = kc.link && !cols_filled_ && !plane_;
   // Several ranks: every poll is a flag all-reduce on the compute stream
   // (latency-bound), so poll half as often; a stop is still exact and at most
   // two windows late.
@@ -176,11 +194,12 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // Boundary-triggered sends (overlap = 3; last_block_trigger): row strips
   // on a backend that can count boundary groups done.  Byte tiles on bit
   // words too: the trigger runs on the bit image.
-  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger();
+  // Not on the plane (the trigger rides on linked launches).
+  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger() && !plane_;
   trigger_ = trigger_ok && cfg_.overlap == 3;
   watchdog_s_ = cfg_.watchdog_s > 0 ? cfg_.watchdog_s : cfg_.tune.f("watchdog_s") > 0 ? cfg_.tune.f("watchdog_s") : 900.0;
   use_graphs_ = cfg_.graphs != 0 && be_->supports_graphs() && tr_->capturable() &&
-                (cfg_.graphs > 0 || tr_->size() == 1);
+                (cfg_.graphs > 0 || tr_->size() == 1) && !plane_;
   if (use_graphs_) gen_dev_ = Owned<int64_t>(be_, be_->alloc(sizeof(int64_t)));
   if (use_graphs_) trigger_ = false;  // captured epochs stay on one stream
   // Overlap auto: measure both schedules on the real ranks (see auto_choose);
@@ -222,7 +241,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // a torus that is the same from block to block).  Everything else keeps
   // today's path.
   const Backend::QuietTuning qt = be_->quiet_mode();
-  if (qt.mode != 0 && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
+  if (qt.mode != 0 && !plane_ && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
       tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_ && tmax_ == be_->quiet_block() && D_ == tmax_) {
     quiet_.mode = qt.mode;
     quiet_.scout = qt.scout;
@@ -232,7 +251,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Lazy tail (run_impl): single-rank ring tiles whose epochs are one block.
   tail_mode_ = cfg_.tune.i("lazy_tail");
-  tail_ok_ = tail_mode_ != 0 && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
+  tail_ok_ = tail_mode_ != 0 && !plane_ && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
   if (tail_ok_) carry_ = Owned<uint32_t>(be_, be_->alloc(size_t(tmax_) * 4));
   gen_ = cfg_.start_gen;
 }
@@ -342,24 +361,27 @@ void Engine::fill(void* buf, const TileGeom& g, bool cols, bool rows) {
 // (RCCL has no strided datatype, unlike the reference's MPI_Type_vector column).
 void Engine::exchange_columns(void* buf, const TileGeom& g) {
   auto* base = static_cast<uint8_t*>(buf);
-  auto nb = dec_.neighbors(rank_);
+  const auto nb = neighbors();  // the plane: -1 on a side at the grid's edge, whose halo the kernels mask
   const int64_t H = g.H, pitch = g.pitch;
   void* t = phase_begin(nullptr);
   const int64_t halo = 32 * int64_t(g.hw);
   const int64_t span = g.span_bytes(halo);
   const int64_t r0 = g.row0();
-  be_->copy_2d_async(colbuf_[0], span, base + g.offset(r0, g.cell0()), pitch, span, H);
-  be_->copy_2d_async(colbuf_[1], span, base + g.offset(r0, g.cell0() + g.W - halo), pitch, span, H);
-  std::vector<P2POp> ops = {
-      {true, nb[kWest], colbuf_[0], size_t(span * H)},
-      {false, nb[kEast], colbuf_[3], size_t(span * H)},
-      {true, nb[kEast], colbuf_[1], size_t(span * H)},
-      {false, nb[kWest], colbuf_[2], size_t(span * H)},
-  };
-  tr_->exchange(ops, be_->stream());
-  halo_bytes_ += 2 * span * H;
-  be_->copy_2d_async(base + g.offset(r0, 0), pitch, colbuf_[2], span, span, H);
-  be_->copy_2d_async(base + g.offset(r0, g.cell0() + g.W), pitch, colbuf_[3], span, span, H);
+  const bool west = nb[kWest] >= 0, east = nb[kEast] >= 0;
+  if (west) be_->copy_2d_async(colbuf_[0], span, base + g.offset(r0, g.cell0()), pitch, span, H);
+  if (east) be_->copy_2d_async(colbuf_[1], span, base + g.offset(r0, g.cell0() + g.W - halo), pitch, span, H);
+  // Both operations of a pair go with their peer: with Px == 2 the torus's
+  // west and east neighbour are one rank, and the plane keeps one of the two
+  // pairs, matched in issue order as before.
+  std::vector<P2POp> ops;
+  if (west) ops.push_back({true, nb[kWest], colbuf_[0], size_t(span * H)});
+  if (east) ops.push_back({false, nb[kEast], colbuf_[3], size_t(span * H)});
+  if (east) ops.push_back({true, nb[kEast], colbuf_[1], size_t(span * H)});
+  if (west) ops.push_back({false, nb[kWest], colbuf_[2], size_t(span * H)});
+  if (!ops.empty()) tr_->exchange(ops, be_->stream());
+  halo_bytes_ += (int64_t(west) + int64_t(east)) * span * H;
+  if (west) be_->copy_2d_async(base + g.offset(r0, 0), pitch, colbuf_[2], span, span, H);
+  if (east) be_->copy_2d_async(base + g.offset(r0, g.cell0() + g.W), pitch, colbuf_[3], span, span, H);
   phase_end(kHalo, t, nullptr);
 }
 
@@ -380,8 +402,10 @@ void Engine::halo_exchange_on(void* buf, const TileGeom& g) {
   // owned rows: rows_wrapped_ and rows_ring_ are single-rank tiles) or from
   // the neighbours through the transport.
   const bool cols_local = dec_.Px == 1, rows_local = dec_.Py == 1 && !cfg_.self_exchange;
-  const bool fill_cols = cols_local && cols_filled_;
-  const bool fill_rows = rows_local && !rows_wrapped_ && !rows_ring_;
+  // The plane fills nothing: what lies beyond the grid's edge is masked in
+  // the kernels (BlockArgs::plane), so a single rank moves no data at all.
+  const bool fill_cols = cols_local && cols_filled_ && !plane_;
+  const bool fill_rows = rows_local && !rows_wrapped_ && !rows_ring_ && !plane_;
   // Nothing to move: no stream join either, so linked launches (GOL_LINK)
   // chain across such epochs.
   if (cols_local && rows_local && !fill_cols && !fill_rows) return;
@@ -397,27 +421,32 @@ void Engine::halo_exchange_on(void* buf, const TileGeom& g) {
     fill(buf, g, /*cols=*/true, /*rows=*/false);
   // Phase B: north/south halo rows over the full padded width.
   if (rows_local) {
-    fill(buf, g, /*cols=*/false, /*rows=*/true);
+    if (fill_rows) fill(buf, g, /*cols=*/false, /*rows=*/true);
   } else {
     void* t = phase_begin(nullptr);
-    tr_->exchange(row_ops(buf, g), be_->stream());
+    const std::vector<P2POp> ops = row_ops(buf, g);
+    if (!ops.empty()) tr_->exchange(ops, be_->stream());
     phase_end(kHalo, t, nullptr);
-    halo_bytes_ += 2 * g.Dv * g.pitch;
+    halo_bytes_ += int64_t(ops.size() / 2) * g.Dv * g.pitch;
   }
 }
 
 // North / south halo rows over the full padded width, Dv rows each way.
 std::vector<P2POp> Engine::row_ops(void* buf, const TileGeom& g) const {
   auto* base = static_cast<uint8_t*>(buf);
-  const auto nb = dec_.neighbors(rank_);
+  const auto nb = neighbors();
   const int64_t Dv = g.Dv, H = g.H, pitch = g.pitch;
   const size_t bytes = size_t(Dv * pitch);
-  return {
+  const std::vector<P2POp> all = {
       {true, nb[kNorth], base + Dv * pitch, bytes},        // my top rows -> north's bottom halo
       {false, nb[kSouth], base + (Dv + H) * pitch, bytes},  // south's top rows -> my bottom halo
       {true, nb[kSouth], base + H * pitch, bytes},          // my bottom rows -> south's top halo
       {false, nb[kNorth], base, bytes},                     // north's bottom rows -> my top halo
   };
+  std::vector<P2POp> ops;
+  for (const P2POp& op : all)
+    if (op.peer >= 0) ops.push_back(op);  // the plane: no partner beyond the grid's edge
+  return ops;
 }
 
 void* Engine::bit_scratch(int i) const {
@@ -614,8 +643,18 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
   }
   a.flags_base = flags_base_;
   a.allow_drift = drift_ok_;
-  a.full_width = dec_.Px == 1 && cfg_.W % 32 == 0;
+  a.full_width = dec_.Px == 1 && cfg_.W % 32 == 0 && !plane_;
   a.wrap_rows = rows_wrapped_;
+  if (plane_) {
+    // The grid's edge in this tile's padded coordinates; a side that borders
+    // another rank's tile gets the tile's own bound, which masks nothing.
+    const auto nb = neighbors();
+    a.plane = true;
+    a.grid_row_lo = nb[kNorth] < 0 ? g.Dv : 0;
+    a.grid_row_hi = nb[kSouth] < 0 ? g.Dv + g.H : g.R();
+    a.grid_cell_lo = nb[kWest] < 0 ? g.cell0() : 0;
+    a.grid_cell_hi = nb[kEast] < 0 ? g.cell0() + g.W : 32 * g.Wp();
+  }
   // Linked launches assume the device to themselves: not while transport
   // work may run beside them on the comm stream (side polls).  The trigger
   // schedule links: its sends start only once the boundary groups are done,

@@ -59,6 +59,8 @@ struct Options {
   std::string layout = "auto";  // auto | bits | u8
   Rule rule;                    // --rule (default B3/S23)
   bool rule_set = false;
+  Boundary boundary = Boundary::Torus;  // --boundary
+  bool boundary_set = false;
   std::string decomp = "auto";
   std::string comm = "auto";  // auto | thread | rccl (in-process ranks)
   std::string output;  // default: the matching reference build's file (see default_output)
@@ -94,6 +96,9 @@ struct Options {
                "                              life, highlife, daynight, seeds, replicator, lwod, 34life\n"
                "                              (default B3/S23; no B0; the hip engine runs the named ones,\n"
                "                              the cpu and ref engines any)\n"
+               "  --boundary torus|dead       what lies beyond the grid's edge: the torus wraps (default);\n"
+               "                              dead = a bounded plane whose outside is dead in every\n"
+               "                              generation (hip engine: B3/S23 only; no lds kernels, graphs)\n"
                "  --gens N                    GEN_LIMIT (default 1000)\n"
                "  --sim-freq F                SIMILARITY_FREQUENCY (default 3)\n"
                "  --no-similarity             disable the similarity check\n"
@@ -146,6 +151,7 @@ Options parse(int argc, char** argv) {
       o.u8_compute = v == "bits" ? 1 : v == "bytes" ? 0 : -1;
     }
     else if (a == "--rule") o.rule = parse_rule(next()), o.rule_set = true;
+    else if (a == "--boundary") o.boundary = parse_boundary(next()), o.boundary_set = true;
     else if (a == "--decomp") o.decomp = next();
     else if (a == "--comm") o.comm = next();
     else if (a == "--gens") o.gens = std::atoll(next().c_str()), o.gens_set = true;
@@ -209,6 +215,12 @@ Options parse(int argc, char** argv) {
     if (o.rule_set && o.rule != ck_rule)
       throw Error("--resume: checkpoint was taken with --rule " + m.rule + ", not " + rule_string(o.rule));
     o.rule = ck_rule;
+    // So is the boundary.
+    const Boundary ck_boundary = parse_boundary(m.boundary);
+    if (o.boundary_set && o.boundary != ck_boundary)
+      throw Error("--resume: checkpoint was taken with --boundary " + m.boundary + ", not " +
+                  boundary_name(o.boundary));
+    o.boundary = ck_boundary;
     o.W = m.W;
     o.H = m.H;
     o.input = checkpoint_grid_path(o.resume);
@@ -286,7 +298,8 @@ int run(const Options& o) {
       read_text_grid(o.input, o.W, o.H, grid);
     }
     read_ms = ms_since(t0);
-    RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule);
+    RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule,
+                                     o.boundary);
     res.generations = rr.generations;
     res.loop_ms = rr.loop_ms;
     res.executed = rr.generations;
@@ -303,6 +316,7 @@ int run(const Options& o) {
     cfg.H = o.H;
     cfg.layout = layout;
     cfg.rule = o.rule;
+    cfg.boundary = o.boundary;
     cfg.decomp = o.decomp;
     cfg.gen_limit = o.gens;
     cfg.check_similarity = o.similarity;
@@ -458,6 +472,7 @@ int run(const Options& o) {
         m.sim_freq = o.sim_freq;
         m.layout = layout_name(layout);
         m.rule = rule_string(o.rule);
+        m.boundary = boundary_name(o.boundary);
         // Fault injection (tests): die after the N-th checkpoint's tiles are
         // written, before it is committed.
         if (const int c = o.tune.i("fault_checkpoint_crash"))
@@ -498,6 +513,7 @@ int run(const Options& o) {
       tuning_changed += "}";
       f << "{\"engine\": " << jstr(engine) << ", \"backend\": " << jstr(backends[0]->name())
         << ", \"layout\": " << jstr(layout_name(layout)) << ", \"rule\": " << jstr(rule_string(o.rule))
+        << ", \"boundary\": " << jstr(boundary_name(o.boundary))
         << ", \"ranks\": " << P
         << ", \"decomp\": " << jstr(engines[0]->decomp().describe()) << ", \"tuning\": " << jstr(o.tune.summary())
         << ", \"tuning_changed\": " << tuning_changed << ", \"W\": " << o.W

@@ -15,8 +15,8 @@ import os
 import sys
 import time
 
-from .models.life import (DEFAULT_RULE, LifeConfig, Simulation, make_backend, parse_rule, parse_tune_args,
-                          reference_run)
+from .models.life import (DEFAULT_BOUNDARY, DEFAULT_RULE, LifeConfig, Simulation, make_backend, parse_rule,
+                          parse_tune_args, reference_run)
 from .utils.metrics import stdout_lines, write_json
 
 
@@ -33,6 +33,9 @@ def parse_args(argv=None):
                    help="Life-like rule: B<digits>/S<digits> (e.g. B36/S23) or a name (life, highlife, daynight, "
                         "seeds, replicator, lwod, 34life); default B3/S23, no B0; the hip engine runs the named "
                         "ones, the cpu and ref engines any")
+    p.add_argument("--boundary", default=None, choices=["torus", "dead"],
+                   help="what lies beyond the grid's edge: torus wraps (default); dead = a bounded plane whose "
+                        "outside is dead in every generation (hip engine: B3/S23 only, no lds kernels, no graphs)")
     p.add_argument("--gens", type=int, default=1000, help="GEN_LIMIT")
     p.add_argument("--sim-freq", type=int, default=None, help="SIMILARITY_FREQUENCY (default 3)")
     p.add_argument("--no-similarity", action="store_true")
@@ -97,6 +100,7 @@ def main(argv=None) -> int:
         rule = parse_rule(a.rule) if a.rule is not None else DEFAULT_RULE
     except RuntimeError as e:
         raise SystemExit(f"--rule: {e}")
+    boundary = a.boundary or DEFAULT_BOUNDARY
     seed, density = 1, 0.5
     if a.random is not None:
         s, _, d = a.random.partition(":")
@@ -112,7 +116,7 @@ def main(argv=None) -> int:
         grid = random_grid(a.width, a.height, seed, density) if a.random else read_grid(a.input_file, a.width, a.height)
         read_ms = (time.perf_counter() - t0) * 1e3
         out, gens, ms = reference_run(np.asarray(grid), a.gens, not a.no_similarity, a.sim_freq, max(1, a.threads),
-                                      rule=rule)
+                                      rule=rule, boundary=boundary)
         t1 = time.perf_counter()
         if a.output != "none":
             write_grid(a.output, out)
@@ -143,7 +147,7 @@ def main(argv=None) -> int:
     cfg = LifeConfig(a.width, a.height, gen_limit=a.gens, check_similarity=not a.no_similarity,
                      sim_freq=a.sim_freq, layout=a.layout, decomp=a.decomp, tmax=a.tmax,
                      epoch=a.epoch, poll_gens=a.poll, overlap=a.overlap, graphs=a.graphs,
-                     u8_compute=a.u8_compute, tune=tune, rule=rule)
+                     u8_compute=a.u8_compute, tune=tune, rule=rule, boundary=boundary)
     src = a.input_file
     if a.resume:
         from .utils.checkpoint import load_checkpoint  # noqa: PLC0415
@@ -152,6 +156,8 @@ def main(argv=None) -> int:
                                          epoch=a.epoch, poll_gens=a.poll, gen_limit=a.gens)
         if a.rule is not None and rule != parse_rule(cfg.rule):
             raise SystemExit(f"--resume: checkpoint was taken with --rule {cfg.rule}, not {rule}")
+        if a.boundary is not None and a.boundary != cfg.boundary:
+            raise SystemExit(f"--resume: checkpoint was taken with --boundary {cfg.boundary}, not {a.boundary}")
         if a.sim_freq_given and not a.no_similarity and a.sim_freq != cfg.sim_freq:
             raise SystemExit(f"--resume: checkpoint was taken with --sim-freq {cfg.sim_freq}; resuming with "
                              f"--sim-freq {a.sim_freq} would shift the similarity checks")

@@ -38,6 +38,7 @@ class LifeConfig:
     sim_freq: int = 3
     layout: str = "auto"        # auto | bits | u8
     rule: str = "B3/S23"        # Life-like rule: B<digits>/S<digits> or a name of gol_amd.RULES (no B0)
+    boundary: str = "torus"     # torus | dead: the grid wraps, or is a bounded plane whose outside is always dead
     decomp: str = "auto"        # auto | PxQ
     tmax: int = 0               # generations per kernel launch (0 = the backend's choice: bits 12 adder /
                                 # 16 DPP; u8 32 / 24 / 16 by tile size)
@@ -73,6 +74,7 @@ class LifeConfig:
         c.H = int(self.height)
         c.layout = C.Layout.Bits if self.resolved_layout() == "bits" else C.Layout.U8
         c.rule = str(self.rule)
+        c.boundary = str(self.boundary)
         c.decomp = self.decomp
         c.gen_limit = int(self.gen_limit)
         c.check_similarity = bool(self.check_similarity)
@@ -94,6 +96,7 @@ class LifeConfig:
 
 
 DEFAULT_RULE = "B3/S23"
+DEFAULT_BOUNDARY = "torus"
 
 
 def parse_rule(rule: str) -> str:
@@ -243,7 +246,8 @@ class Simulation:
         d = self._eng.decomp
         g = self._eng.compute_geom  # the tile the temporal blocks run on (halos)
         return {"backend": self.backend.name(), "transport": self.transport.name(),
-                "layout": self.config.resolved_layout(), "rule": self._eng.config.rule, "decomp": d.describe(),
+                "layout": self.config.resolved_layout(), "rule": self._eng.config.rule,
+                "boundary": self._eng.config.boundary, "decomp": d.describe(),
                 "rank": self.rank, "ranks": d.nranks(), "tile_rows": g.H, "tile_cols": g.W,
                 "halo_rows": g.Dv, "halo_words": g.hw, "tmax": self._eng.tmax,
                 "epoch": self._eng.epoch_depth, "pitch": self._eng.geom.pitch, "overlap": self._eng.overlap(),
@@ -256,6 +260,7 @@ class Simulation:
                                              "side_steady": self._eng.poll_trial_ms_side_steady},
                 "triggered_sends": self._eng.triggered_sends(),
                 "u8_compute": ("bits" if self._eng.via_bits else "bytes") if self.config.resolved_layout() == "u8" else None,
+                "drifting": bool(self._eng.drifting),
                 "row_ring": bool(self._eng.row_ring), "row_ring_fallback": self._eng.row_ring_fallback or None,
                 "kernel": self._kernel_name(),
                 # Quiet-tile skipping (tuning quiet_skip): the mode, T-generation blocks run by
@@ -315,6 +320,12 @@ class Simulation:
             parts.append("row ring (no halo fills)")
         if e.config.rule != DEFAULT_RULE:
             parts.append(f"rule {e.config.rule}")
+        if e.config.boundary != DEFAULT_BOUNDARY:
+            # The plane's kernels: the DPP window whatever xlane asks for, T <= 16 in both layouts.
+            parts.append(f"boundary {e.config.boundary} (bounded plane: edge masked in the temporal blocks, T <= 16)")
+            pk = self.backend.plane_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
+            if pk:
+                parts.append(f"plane kernels: {pk}")
         return ", ".join(parts)
 
     # -- state -----------------------------------------------------------
@@ -380,11 +391,14 @@ def simulate(grid: np.ndarray, gens: int, engine: str = "auto", layout: str = "a
 
 
 def reference_run(grid: np.ndarray, gen_limit: int = 1000, check_similarity: bool = True,
-                  sim_freq: int = 3, threads: int = 1, rule: str = DEFAULT_RULE) -> tuple[np.ndarray, int, float]:
+                  sim_freq: int = 3, threads: int = 1, rule: str = DEFAULT_RULE,
+                  boundary: str = DEFAULT_BOUNDARY) -> tuple[np.ndarray, int, float]:
     """Exact eager serial loop of src/game.c (native), under any Life-like
-    ``rule`` without B0.  Returns (grid, gens, ms)."""
+    ``rule`` without B0, on the torus or (``boundary="dead"``) the bounded
+    plane.  Returns (grid, gens, ms)."""
     gens, ms, out = native().cpu_reference_run(np.ascontiguousarray(grid, dtype=np.uint8), int(gen_limit),
-                                               bool(check_similarity), int(sim_freq), int(threads), str(rule))
+                                               bool(check_similarity), int(sim_freq), int(threads), str(rule),
+                                               str(boundary))
     return out, int(gens), float(ms)
 
 

@@ -6,6 +6,9 @@
                       circular padding (the oracle SURVEY 4.3 T1 prescribes;
                       runs on CPU or on the GPU).
 ``life_step_numpy`` - NumPy ``roll``-sum reference.
+
+Every one of them takes ``boundary="torus"`` (default) or ``"dead"``, the
+bounded plane whose outside is dead in every generation.
 """
 from __future__ import annotations
 
@@ -21,26 +24,42 @@ def rule_masks(rule: str = "B3/S23") -> tuple[int, int]:
 
 
 def life_step(grid: np.ndarray, gens: int = 1, engine: str = "auto", layout: str = "auto",
-              tmax: int = 0, epoch: int = 0, device: int = 0, rule: str = "B3/S23") -> np.ndarray:
+              tmax: int = 0, epoch: int = 0, device: int = 0, rule: str = "B3/S23",
+              boundary: str = "torus") -> np.ndarray:
     """Advance ``grid`` (H x W, 0/1 uint8) by exactly ``gens`` generations."""
     from ..models.life import LifeConfig, Simulation  # noqa: PLC0415
 
     g = np.ascontiguousarray(grid, dtype=np.uint8)
     H, W = g.shape
-    cfg = LifeConfig(W, H, gen_limit=int(gens), layout=layout, tmax=tmax, epoch=epoch, rule=rule)
+    cfg = LifeConfig(W, H, gen_limit=int(gens), layout=layout, tmax=tmax, epoch=epoch, rule=rule,
+                     boundary=boundary)
     sim = Simulation(cfg, engine=engine, device=device)
     sim.load(g)
     sim.advance(int(gens))
     return sim.tile()
 
 
-def life_step_numpy(grid: np.ndarray, gens: int = 1, rule: str = "B3/S23") -> np.ndarray:
+def _check_boundary(boundary: str) -> bool:
+    """True for the bounded plane."""
+    if boundary not in ("torus", "dead"):
+        raise ValueError(f"bad boundary {boundary!r} (want torus or dead)")
+    return boundary == "dead"
+
+
+def life_step_numpy(grid: np.ndarray, gens: int = 1, rule: str = "B3/S23", boundary: str = "torus") -> np.ndarray:
     birth, survive = rule_masks(rule)
+    dead = _check_boundary(boundary)
     lut = np.array([[(birth >> n) & 1 for n in range(9)], [(survive >> n) & 1 for n in range(9)]], dtype=np.uint8)
     g = (np.asarray(grid) != 0).astype(np.uint8)
+    H, W = g.shape
     for _ in range(gens):
-        n = sum(np.roll(np.roll(g, dy, 0), dx, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
-                if (dy, dx) != (0, 0))
+        if dead:  # a moat of dead cells, rebuilt every generation: nothing is ever born in it
+            p = np.pad(g, 1)
+            n = sum(p[1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+                    if (dy, dx) != (0, 0))
+        else:
+            n = sum(np.roll(np.roll(g, dy, 0), dx, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+                    if (dy, dx) != (0, 0))
         g = lut[g, n]
     return g
 
@@ -60,24 +79,25 @@ def _torch_rule(n, t, birth: int, survive: int):
     return torch.where(t == 1, stay, born)
 
 
-def life_step_torch(grid, gens: int = 1, device: str = "cpu", rule: str = "B3/S23"):
+def life_step_torch(grid, gens: int = 1, device: str = "cpu", rule: str = "B3/S23", boundary: str = "torus"):
     """fp32 PyTorch reference of a Life-like rule (default B3/S23) on a torus
-    (conv2d, circular pad)."""
+    (conv2d, circular pad) or the bounded plane (conv2d on a zero-padded input)."""
     import torch  # noqa: PLC0415
     import torch.nn.functional as F  # noqa: PLC0415
 
     birth, survive = rule_masks(rule)
+    dead = _check_boundary(boundary)
 
     t = torch.as_tensor(np.asarray(grid) != 0, dtype=torch.float32, device=device)[None, None]
     k = torch.ones(1, 1, 3, 3, dtype=torch.float32, device=device)
     k[0, 0, 1, 1] = 0.0
     for _ in range(gens):
-        n = F.conv2d(F.pad(t, (1, 1, 1, 1), mode="circular"), k)
+        n = F.conv2d(F.pad(t, (1, 1, 1, 1)) if dead else F.pad(t, (1, 1, 1, 1), mode="circular"), k)
         t = _torch_rule(n, t, birth, survive).to(torch.float32)
     return t[0, 0].to(torch.uint8).cpu().numpy()
 
 
-def life_step_torch_roll(grid, gens: int = 1, device: str = "cpu", rule: str = "B3/S23"):
+def life_step_torch_roll(grid, gens: int = 1, device: str = "cpu", rule: str = "B3/S23", boundary: str = "torus"):
     """fp32 PyTorch reference of a Life-like rule on a torus from elementwise ops only
     (separable neighbour sums of rolled copies, no convolution library): the
     verification oracle for whole-benchmark grids, where a first conv2d call
@@ -85,10 +105,20 @@ def life_step_torch_roll(grid, gens: int = 1, device: str = "cpu", rule: str = "
     import torch  # noqa: PLC0415
 
     birth, survive = rule_masks(rule)
+    dead = _check_boundary(boundary)
     t = torch.as_tensor(np.asarray(grid) != 0, dtype=torch.float32, device=device)
+
+    def shifted(a, s, dim):
+        """``a`` rolled by ``s`` along ``dim``; on the bounded plane the row or
+        column that rolled in from the other side is dead."""
+        r = torch.roll(a, s, dim)
+        if dead:
+            r.select(dim, 0 if s > 0 else -1).zero_()
+        return r
+
     for _ in range(gens):
-        h = t + torch.roll(t, 1, 1) + torch.roll(t, -1, 1)
-        n = h + torch.roll(h, 1, 0) + torch.roll(h, -1, 0) - t
+        h = t + shifted(t, 1, 1) + shifted(t, -1, 1)
+        n = h + shifted(h, 1, 0) + shifted(h, -1, 0) - t
         t = _torch_rule(n, t, birth, survive).to(torch.float32)
         del h, n
     return t.to(torch.uint8).cpu().numpy()

@@ -25,7 +25,7 @@ import re
 from pathlib import Path
 from typing import Optional
 
-from ..models.life import DEFAULT_RULE, LifeConfig, RunReport, Simulation, parse_rule
+from ..models.life import DEFAULT_BOUNDARY, DEFAULT_RULE, LifeConfig, RunReport, Simulation, parse_rule
 from .termination import reported_generations, sim_phase_at
 
 
@@ -70,6 +70,12 @@ def _fsync(path: Path, directory: bool = False) -> None:
         os.close(fd)
 
 
+def _boundary(text: str) -> str:
+    if text not in ("torus", "dead"):
+        raise ValueError(f"checkpoint: bad boundary {text!r} (want torus or dead)")
+    return text
+
+
 def save_checkpoint(sim: Simulation, directory: str, is_root: bool = True, barrier=None) -> Path:
     d = Path(directory)
     if is_root:
@@ -96,6 +102,9 @@ def save_checkpoint(sim: Simulation, directory: str, is_root: bool = True, barri
     rule = parse_rule(cfg.rule)
     if rule != DEFAULT_RULE:
         meta = {k: v for k, v in meta.items() if k != "grid"} | {"rule": rule, "grid": name}
+    # "boundary" likewise, only when it is not the torus (a missing key means the torus).
+    if cfg.boundary != DEFAULT_BOUNDARY:
+        meta = {k: v for k, v in meta.items() if k != "grid"} | {"boundary": _boundary(cfg.boundary), "grid": name}
     grid = d / name
     if is_root:
         from .io import create_text_file  # noqa: PLC0415
@@ -139,7 +148,8 @@ def load_checkpoint(directory: str, **overrides) -> tuple[LifeConfig, Path]:
     cfg = LifeConfig(meta["width"], meta["height"], gen_limit=meta["gen_limit"],
                      check_similarity=meta["check_similarity"], sim_freq=meta["sim_freq"],
                      layout=meta.get("layout", "auto"), start_gen=meta["generation"],
-                     sim_phase=meta["sim_phase"], rule=parse_rule(meta.get("rule", DEFAULT_RULE)))
+                     sim_phase=meta["sim_phase"], rule=parse_rule(meta.get("rule", DEFAULT_RULE)),
+                     boundary=_boundary(meta.get("boundary", DEFAULT_BOUNDARY)))
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg, d / _meta_grid(meta, d)
