@@ -158,7 +158,8 @@ class Backend {
     bool link = false;  // consecutive blocks may run linked (BlockArgs::link)
   };
   virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req,
-                                     Rule /*rule*/ = Rule{}, Boundary boundary = Boundary::Torus) const {
+                                     Rule /*rule*/ = Rule{}, Boundary boundary = Boundary::Torus,
+                                     bool /*census*/ = false) const {
     return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && boundary == Boundary::Torus};
   }
   // Quiet-tile skipping (BlockArgs::quiet, gol/quiet.hpp).  quiet_mode(): the
@@ -213,6 +214,17 @@ class Backend {
   // Description of the kernels that run the bounded plane ("" where the
   // backend has one kind only).
   virtual std::string plane_kernel(Layout) const { return ""; }
+  // Whether run_block honours BlockArgs::census (the per-generation population
+  // census) on tiles of this layout with `rule` and boundary `b`;
+  // unsupported_census() is the message of the engine's refusal and names the
+  // combination.
+  virtual bool supports_census(Layout, Rule, Boundary) const { return false; }
+  virtual std::string unsupported_census(Layout, Rule, Boundary) const {
+    return "backend " + name() + " does not run census=1";
+  }
+  // Description of the kernels that run a census engine ("" where the backend
+  // has one kind only).
+  virtual std::string census_kernel(Layout) const { return ""; }
   // Row ring (single-rank torus): a tile whose top Dv halo rows are a second
   // virtual mapping of its last Dv owned rows and whose bottom halo rows map
   // its first ones, so the periodic row halos are always valid and never

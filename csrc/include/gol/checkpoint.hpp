@@ -43,6 +43,10 @@ struct CheckpointMeta {
   // carries a "boundary" key only when it is not the torus; a missing key
   // means the torus.
   std::string boundary = "torus";
+  // EngineConfig::census.  meta.json carries a "census" key only when it is
+  // on; a missing key means off.  The series itself is per run and is not
+  // checkpointed.
+  bool census = false;
   std::string grid = "grid.txt";  // grid file name inside the checkpoint directory
 };
 

@@ -16,6 +16,7 @@ namespace gol {
 struct RefResult {
   int64_t generations = 0;
   double loop_ms = 0;
+  std::vector<int64_t> population;  // cpu_reference_run(..., census = true)
 };
 
 // `grid` holds H*W cells (0/1 or ASCII) and is overwritten with the final
@@ -25,8 +26,10 @@ struct RefResult {
 // itself is B3/S23 only): the exact oracle for "Generations" under any rule.
 // `boundary`: Boundary::Dead counts neighbours outside the grid as dead (the
 // bounded plane) instead of wrapping around the torus.
+// `census`: RefResult::population receives the live cells of every generation
+// the loop advanced through (entry i: generation 1 + i; `generations` entries).
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
                             bool check_similarity, int sim_freq, int threads, Rule rule = Rule{},
-                            Boundary boundary = Boundary::Torus);
+                            Boundary boundary = Boundary::Torus, bool census = false);
 
 }  // namespace gol

@@ -39,6 +39,13 @@ struct EngineConfig {
   // linked or chained launches, no quiet-tile skipping, no lazy tail, no
   // periodic fills; ranks exchange halos only across edges between ranks.
   Boundary boundary = Boundary::Torus;
+  // Population census: every run also returns the number of live cells of
+  // every generation it advanced through (RunResult::population), counted
+  // inside the temporal blocks (BlockArgs::census) and summed over ranks.  Off
+  // by default, and nothing changes when off.  A census engine runs no linked
+  // or chained launches, no quiet-tile skipping, no lazy tail, no boundary
+  // trigger and no graphs.
+  bool census = false;
   std::string decomp = "auto";     // "auto" or "PxQ"
   int64_t gen_limit = 1000;        // GEN_LIMIT (src/game.c:6)
   bool check_similarity = true;    // CHECK_SIMILARITY (src/game.c:8)
@@ -131,6 +138,10 @@ struct RunResult {
   // can exceed loop_ms; the rest of loop_ms is host gaps and idle device.
   bool phase_timed = false;
   double compute_ms = 0, halo_ms = 0, fill_ms = 0, allreduce_ms = 0;
+  // EngineConfig::census: entry i is the live cells of the whole grid (the sum
+  // over ranks, on every rank) at generation g0 + 1 + i, g0 the generation the
+  // run started at; exactly Engine::generation() - g0 entries.  Empty when off.
+  std::vector<int64_t> population;
 };
 
 // The reference's "Generations:" value of a run over (start_gen, limit] whose
@@ -442,6 +453,11 @@ class Engine {
   int64_t gen_ = 0;
   int64_t exchanges_ = 0, polls_ = 0, launches_ = 0;
   bool plane_ = false;      // EngineConfig::boundary == Boundary::Dead
+  // EngineConfig::census: the device window of per-generation counts, parallel
+  // to flags_ (same base and length, zeroed with it), and whether a run is
+  // filling it (launches outside a run - step_block - count nothing).
+  Owned<uint64_t> census_;
+  bool census_run_ = false;
   bool drift_ok_ = false;   // whole-width tile of 32-cell words on a drifting backend
   bool cols_filled_ = true; // column halos kept valid by fills (false: the backend wraps column reads)
   bool rows_wrapped_ = false; // single-rank torus read modulo its rows (no fills at all)

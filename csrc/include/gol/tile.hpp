@@ -120,6 +120,12 @@ struct BlockArgs {
   // together with allow_drift, wrap_rows, full_width, link, ring or quiet.
   bool plane = false;
   int64_t grid_row_lo = 0, grid_row_hi = 0, grid_cell_lo = 0, grid_cell_hi = 0;
+  // Census (EngineConfig::census): a window of 64-bit counts in the backend's
+  // address space, one per generation, addressed like `changed` (entry
+  // gen_base + L - flags_base for generation gen_base + L); the block adds the
+  // live cells of the tile's owned rows and cells at each of its generations
+  // L = 1..T.  Null: no census.  Never set together with link, quiet or gen_dev.
+  uint64_t* census = nullptr;
 };
 
 }  // namespace gol

@@ -53,6 +53,8 @@ class Transport {
   virtual void exchange(const std::vector<P2POp>& ops, void* stream) = 0;
   // In-place element-wise MAX over ranks of n uint32 values.
   virtual void allreduce_max_u32(uint32_t* buf, size_t n, void* stream) = 0;
+  // In-place element-wise SUM over ranks of n uint64 values (the census series).
+  virtual void allreduce_sum_u64(uint64_t* buf, size_t n, void* stream) = 0;
   virtual void barrier() = 0;
   // exchange()/allreduce enqueue device work only (no host waits), so they
   // can be captured into a HIP graph.
@@ -80,6 +82,7 @@ class SelfTransport final : public Transport {
   const char* name() const override { return "self"; }
   void exchange(const std::vector<P2POp>& ops, void* stream) override;
   void allreduce_max_u32(uint32_t*, size_t, void*) override {}
+  void allreduce_sum_u64(uint64_t*, size_t, void*) override {}
   void barrier() override {}
   bool capturable() const override { return true; }
 };
@@ -103,6 +106,7 @@ class ThreadHub {
   int arrived = 0;
   uint64_t generation = 0;
   std::vector<uint32_t> red;
+  std::vector<uint64_t> red64;  // allreduce_sum_u64
 
  private:
   int n_;
@@ -117,6 +121,7 @@ class ThreadTransport final : public Transport {
   const char* name() const override { return "thread"; }
   void exchange(const std::vector<P2POp>& ops, void* stream) override;
   void allreduce_max_u32(uint32_t* buf, size_t n, void* stream) override;
+  void allreduce_sum_u64(uint64_t* buf, size_t n, void* stream) override;
   void barrier() override;
   // Tuning cpu_side_poll=1 (tests): claims a flag reduction of its own, so the
   // engine's poll placement trial runs on CPU ranks (both placements reduce

@@ -74,6 +74,14 @@ std::string life_block_plane_variant(Layout layout, const LifeTuning& tune) {
          (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "");
 }
 
+std::string life_block_census_variant(Layout layout, const LifeTuning& tune) {
+  const bool grouped = tune.group != 0;
+  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp census" +
+         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window with the census)" : "") +
+         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "") +
+         (tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)";
+}
+
 int life_block_max_T(Layout layout, const LifeTuning& tune) {
   if (layout == Layout::U8 && tune.u8_lds) return tune.lds_T;
   // Register budget for 2 waves/SIMD (<= 256 VGPRs): T <= 16 (one word per lane).
@@ -141,6 +149,26 @@ LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const
     const int64_t gtail = a.grid_cell_hi % 32;
     p.grid_last_mask = gtail ? (0xFFFFFFFFu >> (32 - gtail)) : 0xFFFFFFFFu;
     return (g.layout == Layout::U8 ? launch_plane_u8_dpp : launch_plane_bits_dpp)(p, rows, a.T, tune, ctx, stream);
+  }
+  if (a.census) {
+    // The census: lb::CensusIO kernels, B3/S23 on the torus with the DPP window
+    // (a forced adder window runs the DPP window too).  Wrapped column reads
+    // and the row ring stay: the owned words and rows are counted once either
+    // way.  The engine refuses the combinations that have no census kernel
+    // before any launch; these guard the launcher itself.
+    GOL_REQUIRE(rule_is_default(a.rule), "life_block: census runs B3/S23 only on the HIP engine");
+    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: census with u8_kernel=lds");
+    GOL_REQUIRE(!a.allow_drift && !a.wrap_rows && !a.link && !a.quiet && !a.gen_dev,
+                "life_block: census with a launch option it does not run with");
+    GOL_REQUIRE(a.T <= 16, "life_block: census kernels run temporal blocks of at most 16 generations");
+    // A wave's count of one generation stays below 2^31 (64 lanes x 32 cells x rows).
+    GOL_REQUIRE(rows + 2 * a.T < (int64_t(1) << 20), "life_block: census needs blocks of fewer than 2^20 rows");
+    GOL_REQUIRE(a.gen_base >= a.flags_base, "life_block: census block before its window");
+    p.link_ring_rows = 0;
+    p.grid_row_lo = int(g.Dv);
+    p.grid_row_hi = int(g.Dv + g.H);
+    p.census = reinterpret_cast<unsigned long long*>(a.census) + (a.gen_base + 1 - a.flags_base);
+    return (g.layout == Layout::U8 ? launch_census_u8_dpp : launch_census_bits_dpp)(p, rows, a.T, tune, ctx, stream);
   }
   int x = tune.xlane == kXlaneAdd || tune.xlane == kXlaneAuto ? tune.xlane : kXlaneDpp;
   // Any rule but B3/S23: the kernels compiled from life_rules.def.

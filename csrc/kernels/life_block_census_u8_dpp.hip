@@ -1,0 +1,4 @@
+// Census kernels (per-generation live-cell counts), variant u8_dpp: see life_block_launch.hpp.
+#include "life_block_launch.hpp"
+
+GOL_CENSUS_TU_U8_DPP

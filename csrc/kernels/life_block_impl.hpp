@@ -366,6 +366,7 @@ template <int W_, int XL_, class Rule_ = Conway>
 struct BitsIO {
   using Rule = Rule_;
   using Edge = Torus;  // PlaneIO
+  static constexpr bool kCensus = false;  // CensusIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = 1;  // halo lanes per wave side
   static constexpr bool kLinked = false;  // Sc1IO
@@ -409,6 +410,7 @@ template <int W_, int XL_, int HALO_ = 1, class Rule_ = Conway>
 struct U8IO {
   using Rule = Rule_;
   using Edge = Torus;  // PlaneIO
+  static constexpr bool kCensus = false;  // CensusIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = HALO_;  // halo lanes per wave side (2: passes deeper than 32)
   static constexpr bool kLinked = false;  // Sc1IO
@@ -500,6 +502,39 @@ struct PlaneIO : IO {
   using Edge = Plane;
 };
 
+// Storage layout of a census launch (BlockArgs::census): IO whose level bodies
+// also count the live cells of every generation of the block (CensusState).  A
+// wrapper like PlaneIO, so the other instantiations keep their names and code.
+template <class IO>
+struct CensusIO : IO {
+  static constexpr bool kCensus = true;
+};
+
+// Census: the second fused per-generation reduction beside the change flags.
+// Every level body adds the live cells of the level row it produced to a
+// per-level, per-lane count - but only where that row is counted by this wave
+// and by no other: the lane's owned cells (LaneCols::fmask: no wave-halo word,
+// no halo column, no bit beyond the tile's last cell) and a wave-uniform row
+// test held in SGPRs like the plane's.  The counted rows [lo, hi) of a wave are
+// rows that the wave (life_block_kernel) or its group (life_group_kernel)
+// evaluates completely at every level, that partition the block's rows between
+// waves or groups, clipped to the tile's owned rows: the redundant triangle rows
+// at segment and group boundaries and the halo rows of a deep-halo epoch fall
+// outside them.  A lane adds at most 32 per level row, so 32 bits hold any
+// wave's count (the launcher keeps a block below 2^20 rows: a wave's total
+// below 2^31).
+template <bool On, int T, int W>
+struct CensusState {};
+template <int T, int W>
+struct CensusState<true, T, W> {
+  uint32_t cnt[T][W];  // [L]: live counted cells of the level-(L+1) rows in the lane's word i
+  uint32_t fm[W];      // LaneCols::fmask
+  int rel;             // the wave's first input row (sweep step 0) minus lo
+  uint32_t rows;       // hi - lo (0: the wave counts nothing)
+  // All ones if the level-L row of sweep step k is counted by this wave (wave-uniform).
+  __device__ __forceinline__ uint32_t row_mask(int k, int L) const { return uint32_t(rel + k - L) < rows ? ~0u : 0u; }
+};
+
 // Row reader with a 3-deep register prefetch: the row for step k sits in
 // slot k % 3 and is replaced by the load for step k + 3 when consumed.
 // Rows in flight per wave: sets of 3 (the window's slots), the oldest set
@@ -546,14 +581,57 @@ struct RowReader {
 
 // Per-wave state.  Level L (0..T-1) keeps, for its last three rows (slot =
 // row index mod 3), the horizontal sums h0/h1 and the cells themselves.
-template <int T, int W, class Edge = Torus>
+template <int T, int W, class Edge = Torus, bool Census = false>
 struct Levels {
   Vec<W> h0[T][3], h1[T][3], cc[T][3];
   Vec<W> acc[T];  // per word: OR of (new ^ old) per produced level L+1
   EdgeState<Edge, W> edge;
+  CensusState<Census, T, W> cen;
 };
 template <int T, class IO>
-using LevelsOf = Levels<T, IO::W, typename IO::Edge>;
+using LevelsOf = Levels<T, IO::W, typename IO::Edge, IO::kCensus>;
+
+// Census: the wave counts the level rows [lo, hi) (padded rows) clipped to the
+// tile's owned rows (LifeBlockParams::grid_row_lo / grid_row_hi of a census
+// launch); in0: the padded row of sweep step 0.
+template <int T, class IO>
+__device__ __forceinline__ void census_init(LevelsOf<T, IO>& st, const LifeBlockParams& p, const LaneCols<IO>& lc,
+                                            int64_t in0, int64_t lo, int64_t hi) {
+  if constexpr (IO::kCensus) {
+#pragma unroll
+    for (int i = 0; i < IO::W; ++i) {
+      st.cen.fm[i] = lc.fmask[i];
+#pragma unroll
+      for (int L = 0; L < T; ++L) st.cen.cnt[L][i] = 0u;
+    }
+    const int64_t c0 = max(lo, int64_t(p.grid_row_lo)), c1 = min(hi, int64_t(p.grid_row_hi));
+    st.cen.rel = int(in0 - c0);
+    st.cen.rows = c1 > c0 ? uint32_t(c1 - c0) : 0u;
+  }
+}
+
+// Census, end of wave: lane L < T gets the wave's count of generation level
+// L + 1 (every other lane 0).
+template <int T, class IO>
+__device__ __forceinline__ uint32_t census_wave_counts(const LevelsOf<T, IO>& st, int lane) {
+  uint32_t mine = 0;
+#pragma unroll
+  for (int L = 0; L < T; ++L) {
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < IO::W; ++i) s += st.cen.cnt[L][i];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += uint32_t(__shfl_xor(int(s), d, 64));
+    if (lane == L) mine = s;
+  }
+  return mine;
+}
+
+// The 64-bit slot of the block's first generation in LifeBlockParams::census
+// (addressed like `changed`).
+__device__ __forceinline__ unsigned long long* census_slots(const LifeBlockParams& p) {
+  return p.gen_dev ? p.census + (*p.gen_dev + p.gen_rel) : p.census;
+}
 
 // Plane: the input row of sweep step k, cells outside the grid cleared.
 template <class IO, class St, int W = IO::W>
@@ -569,7 +647,7 @@ __device__ __forceinline__ Vec<W> edge_input(const St& st, Vec<W> cur, int k) {
 // Level L at a step in slot S: push the new level-L row `cur` into the
 // window and produce the level-(L+1) row one row above it.  k: the sweep
 // step (the level-L row is the wave's first input row + k - L), which only the
-// Plane edge policy looks at.
+// Plane edge policy and the census look at.
 template <int T, class IO, int S, int L, int W = IO::W>
 __device__ __forceinline__ Vec<W> level_full(LevelsOf<T, IO>& st, const Vec<W>& cur_in, int k = 0) {
   constexpr int s1 = (S + 1) % 3, s2 = (S + 2) % 3;
@@ -582,6 +660,12 @@ __device__ __forceinline__ Vec<W> level_full(LevelsOf<T, IO>& st, const Vec<W>& 
     nxt.w[i] = IO::Rule::eval(st.h0[L][s1].w[i], st.h1[L][s1].w[i], st.h0[L][s2].w[i], st.h1[L][s2].w[i], h0.w[i],
                               h1.w[i], ctr);
     if constexpr (IO::Edge::kPlane) nxt.w[i] = bop3<tt::AND3>(nxt.w[i], st.edge.cm[i], st.edge.row_mask(k, L + 1));
+    if constexpr (IO::kCensus) {
+      // One mask op and one accumulating population count per word and level;
+      // the opaque def as for acc[L] below.
+      st.cen.cnt[L][i] += uint32_t(__builtin_popcount(bop3<tt::AND3>(nxt.w[i], st.cen.fm[i], st.cen.row_mask(k, L + 1))));
+      asm("" : "+v"(st.cen.cnt[L][i]));
+    }
     st.acc[L].w[i] = bop3<tt::OR_XOR>(st.acc[L].w[i], nxt.w[i], ctr);
     // Opaque def: in straight-line code (prologue / grouped epilogue) hipcc
     // otherwise reassociates the flag ORs of many steps into one late tree
@@ -722,6 +806,9 @@ void life_block_kernel(const LifeBlockParams p) {
     }
   }
   edge_init<IO>(st.edge, p, lc, o0 - T);
+  // Census: at every level L + 1 <= T the wave evaluates all of its output
+  // rows [o0, o1), and the waves' output rows partition the block.
+  census_init<T, IO>(st, p, lc, o0 - T, o0, o1);
 
   constexpr int kPro = 2 * T;
   const int kend = kPro + int(o1 - o0);
@@ -762,6 +849,14 @@ void life_block_kernel(const LifeBlockParams p) {
     }
     uint32_t* ch = p.gen_dev ? p.changed + (*p.gen_dev + p.gen_rel) : p.changed;
     if (lane < T && ((mask >> lane) & 1u)) ch[lane] = 1u;
+  }
+  // Census: one 64-bit add per generation and wave (no barrier here: the
+  // workgroup's waves are independent and may have left above).
+  if constexpr (IO::kCensus) {
+    const uint32_t mine = census_wave_counts<T, IO>(st, lane);
+    if (lane < T && mine != 0u)
+      __hip_atomic_fetch_add(census_slots(p) + lane, (unsigned long long)mine, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 

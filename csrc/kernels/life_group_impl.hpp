@@ -346,8 +346,8 @@ void life_group_kernel(const LifeBlockParams p) {
   // recomputes its upper neighbour's last row, identically), so the wave's
   // control flow is the same for all of them; lanes carry their group's row
   // offset in their read / store offsets.
-  // fold == 1 (launch_T); rule and plane kernels are never chained (the wait compiles out)
-  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && p.chain_buf != nullptr;
+  // fold == 1 (launch_T); rule, plane and census kernels are never chained (the wait compiles out)
+  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus && p.chain_buf != nullptr;
   int kcol, grp, nsub = 1, sub_lanes = 64;
   if (p.fold > 1 && blk >= (p.ncolw - 1) * p.nseg) {
     kcol = p.ncolw - 1;
@@ -420,6 +420,14 @@ void life_group_kernel(const LifeBlockParams p) {
     }
   }
   edge_init<IO>(st.edge, p, lc, in0);
+  // Census: inside a group every level row is computed exactly once (rows fed
+  // from LDS by the wave below are not evaluated here, so not counted here),
+  // and at every level the group evaluates all of its output rows [G0, G1):
+  // wave 0's classic start reaches level L + 1 at row G0 - T + L + 1 <= G0 and
+  // the last wave's classic end at row G1 - 1 + T - L - 1 >= G1 - 1.  The rows
+  // beyond them are the redundant triangles the neighbouring groups count.
+  // (Census launches are never folded or chained: one group per block.)
+  census_init<T, IO>(st, p, lc, in0, G0, G1);
 
   if constexpr (IO::kLinked) {  // wait for the previous launch's rows this group reads
     // (a folded block: the rows of all its groups)
@@ -483,6 +491,21 @@ void life_group_kernel(const LifeBlockParams p) {
     }
     uint32_t* ch = p.gen_dev ? p.changed + (*p.gen_dev + p.gen_rel) : p.changed;
     if (lane < T && ((mask >> lane) & 1u)) ch[lane] = 1u;
+  }
+  // Census: the workgroup's waves add up in LDS, then one 64-bit add per
+  // generation and group.
+  if constexpr (IO::kCensus) {
+    __shared__ uint32_t cen[M * 16];
+    const uint32_t mine = census_wave_counts<T, IO>(st, lane);
+    if (lane < T) cen[m * 16 + lane] = mine;
+    __syncthreads();
+    if (m == 0 && lane < T) {
+      unsigned long long sum = 0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) sum += cen[j * 16 + lane];
+      if (sum != 0ull)
+        __hip_atomic_fetch_add(census_slots(p) + lane, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   if constexpr (IO::kLinked) {  // every wave's rows are written through, then one flag
     __builtin_amdgcn_s_waitcnt(0);

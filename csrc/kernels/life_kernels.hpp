@@ -140,6 +140,13 @@ struct LifeBlockParams {
   int grid_row_lo, grid_row_hi;
   int grid_w0, grid_w1;
   uint32_t grid_last_mask;
+  // Census (BlockArgs::census; the kernels of lb::CensusIO): the 64-bit slot of
+  // the block's first generation, one slot per generation, addressed like
+  // `changed` (with gen_dev: census + *gen_dev + gen_rel).  Every wave or
+  // group adds its count of each generation's live owned cells.  A census
+  // launch is never a plane launch and passes the tile's owned rows in
+  // grid_row_lo / grid_row_hi.  Null in every other launch.
+  unsigned long long* census;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -345,6 +352,8 @@ bool life_block_has_rule(Rule r);
 std::string life_block_variant(Layout layout, const LifeTuning& tune);
 // The same for a bounded-plane engine (BlockArgs::plane).
 std::string life_block_plane_variant(Layout layout, const LifeTuning& tune);
+// The same for a census engine (BlockArgs::census).
+std::string life_block_census_variant(Layout layout, const LifeTuning& tune);
 // Largest T that keeps 2 waves/SIMD for the variant's words-per-lane.
 int life_block_max_T(Layout layout, const LifeTuning& tune);
 
@@ -360,6 +369,11 @@ GOL_LIFE_VARIANT(launch_u8_w1_add);
 // the adder window's drifting frame is a relabelling of torus columns.
 GOL_LIFE_VARIANT(launch_plane_bits_dpp);
 GOL_LIFE_VARIANT(launch_plane_u8_dpp);
+// The census (lb::CensusIO; life_block_census_*.hip): DPP window only - the
+// adder window would count exactly too (its frame is a relabelling of
+// columns), but it is a second set of kernels.
+GOL_LIFE_VARIANT(launch_census_bits_dpp);
+GOL_LIFE_VARIANT(launch_census_u8_dpp);
 // The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave
 // groups of short segments; life_block_bits_w1_dpp_quiet.hip): wrap-mode
 // blocks over a row ring's owned rows only.  Returns the tiles launched, 0

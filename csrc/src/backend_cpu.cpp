@@ -193,6 +193,9 @@ class CpuBackend final : public Backend {
   bool supports_rule(Layout, Rule) const override { return true; }
   // The bounded plane with any rule (run_block masks every level row).
   bool supports_boundary(Layout, Rule, Boundary) const override { return true; }
+  // The census with any rule, on the torus and the plane (run_block counts
+  // the level rows of its bands).
+  bool supports_census(Layout, Rule, Boundary) const override { return true; }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override;
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t r0,
                     int64_t n) override;
@@ -322,6 +325,10 @@ int CpuBackend::run_block(const BlockArgs& a) {
   const int64_t bs = std::max<int64_t>(4 * int64_t(T), ceil_div(out_rows, 2 * int64_t(pool_.size())));
   const int64_t nb = ceil_div(out_rows, bs);
   std::vector<uint8_t> any(size_t(nb * T), 0);
+  // Census (BlockArgs::census): per band and level, the live owned cells of the
+  // level rows that are the band's own output rows [lo, hi) and the tile's
+  // owned rows - the bands' trapezoids overlap, their output rows do not.
+  std::vector<uint64_t> pops(a.census ? size_t(nb * T) : 0, 0);
   auto* in = static_cast<const uint8_t*>(a.in);
   auto* out = static_cast<uint8_t*>(a.out);
   const int64_t P = Wp + 2;  // row stride of the level buffers: a zero word either side
@@ -373,6 +380,16 @@ int CpuBackend::run_block(const BlockArgs& a) {
             // cells only, which all lie inside the grid.
             clip(dst, lo - T + L + n - 2);
           }
+          if (a.census) {
+            // Before the drift emulation shifts the row: the owned words of
+            // a drifted frame hold every column of the torus once.
+            const int64_t r = lo - T + L + n - 2;
+            if (r >= lo && r < hi && r >= g.Dv && r < g.Dv + g.H) {
+              uint64_t live = 0;
+              for (int64_t c = 0; c < Wp; ++c) live += uint64_t(__builtin_popcount(dst[c] & owned[size_t(c)]));
+              pops[size_t(band * T + L)] += live;
+            }
+          }
           if (!last) {
             hsum_row(dst, Wp, hs0(L + 1, sd), hs1(L + 1, sd));
             ++cnt[size_t(L + 1)];
@@ -399,6 +416,11 @@ int CpuBackend::run_block(const BlockArgs& a) {
       const int64_t idx = a.gen_dev ? *a.gen_dev + a.gen_rel + (L - 1) : a.gen_base + L - a.flags_base;
       if (ch) a.changed[idx] = 1u;
     }
+  if (a.census) {
+    GOL_REQUIRE(!a.gen_dev && a.gen_base >= a.flags_base, "run_block: census block before its window");
+    for (int L = 1; L <= T; ++L)
+      for (int64_t b = 0; b < nb; ++b) a.census[a.gen_base + L - a.flags_base] += pops[size_t(b * T + L - 1)];
+  }
   return drift;
 }
 

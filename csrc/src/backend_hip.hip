@@ -644,7 +644,8 @@ class HipBackend final : public Backend {
     // Rule kernels (any rule but B3/S23) are never linked or chained, forced
     // link=1 / chain=1 included.
     // Nor are the plane's kernels (BlockArgs::plane), which never skip either.
-    const bool conway = rule_is_default(a.rule) && !a.plane;
+    // The census kernels (BlockArgs::census) likewise.
+    const bool conway = rule_is_default(a.rule) && !a.plane && !a.census;
     // Wave trace: launch trace_at_ (its `pair` form: and the next one).
     const int64_t traced = trace_at_ < 0 ? -1 : launches_ - trace_at_;
     const bool trace = traced == 0 || (traced == 1 && trace_pair_);
@@ -799,13 +800,18 @@ class HipBackend final : public Backend {
   // same window and T: their adder kernels keep four waves per SIMD at T = 12
   // (docs/PERFORMANCE.md "Life-like rules").  Their byte kernels stop at
   // T = 16, and they never link.
-  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule,
-                             Boundary boundary) const override {
+  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule, Boundary boundary,
+                             bool census) const override {
     // The bounded plane: the DPP window's choice of T (its kernels stop at
     // T = 16 in both layouts), never drifting, never linked, never skipping.
-    if (boundary == Boundary::Dead) {
+    // The census: the same (its kernels are the DPP window's, T <= 16).
+    if (boundary == Boundary::Dead || census) {
       KernelChoice k = choose_conway(l, rows, cols, tmax_req, hipk::kXlaneDpp);
       k.tmax = std::min(k.tmax, 16);
+      // The bit layout's T = 16 census kernel takes 153 VGPRs (3 waves per
+      // SIMD) where T = 12 takes 122 (4 waves): 32768^2 15.48 against 14.08 ms
+      // per 1000 generations (docs/PERFORMANCE.md "Population census").
+      if (census && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
       k.drift = k.link = false;
       return k;
     }
@@ -847,6 +853,23 @@ class HipBackend final : public Backend {
            "rule on the plane)";
   }
   std::string plane_kernel(Layout l) const override { return hipk::life_block_plane_variant(l, tune_); }
+  // The census: B3/S23 on the torus, the temporal-block kernels of either layout.
+  bool supports_census(Layout l, Rule rule, Boundary b) const override {
+    return b == Boundary::Torus && rule_is_default(rule) && !(l == Layout::U8 && tune_.u8_lds);
+  }
+  std::string unsupported_census(Layout l, Rule rule, Boundary b) const override {
+    if (b != Boundary::Torus)
+      return std::string("census=1 with boundary=") + boundary_name(b) +
+             " on the HIP engine: the census kernels are compiled for the torus only (the cpu and ref engines "
+             "count on the plane)";
+    if (!rule_is_default(rule))
+      return "census=1 with rule " + rule_string(rule) +
+             " on the HIP engine: the census kernels are compiled for B3/S23 only (the cpu and ref engines count "
+             "under any rule)";
+    (void)l;
+    return "census=1 with u8_kernel=lds: the LDS-tiled byte kernels have no census";
+  }
+  std::string census_kernel(Layout l) const override { return hipk::life_block_census_variant(l, tune_); }
   KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req, int xlane) const {
     KernelChoice k{tmax_req > 0 ? tmax_req : preferred_tmax(l), false};
     if (l == Layout::U8 && tmax_req <= 0 && !tune_.u8_lds) {

@@ -34,8 +34,9 @@ class CallbackTransport final : public Transport {
   using ExchangeFn = std::function<void(py::list, std::uintptr_t)>;
   using ReduceFn = std::function<void(std::uintptr_t, size_t, std::uintptr_t)>;
   using BarrierFn = std::function<void()>;
-  CallbackTransport(int rank, int size, ExchangeFn ex, ReduceFn red, BarrierFn bar)
-      : rank_(rank), size_(size), ex_(std::move(ex)), red_(std::move(red)), bar_(std::move(bar)) {}
+  CallbackTransport(int rank, int size, ExchangeFn ex, ReduceFn red, BarrierFn bar, ReduceFn sum)
+      : rank_(rank), size_(size), ex_(std::move(ex)), red_(std::move(red)), bar_(std::move(bar)),
+        sum_(std::move(sum)) {}
   int rank() const override { return rank_; }
   int size() const override { return size_; }
   const char* name() const override { return "callback"; }
@@ -50,6 +51,11 @@ class CallbackTransport final : public Transport {
     py::gil_scoped_acquire gil;
     red_(reinterpret_cast<std::uintptr_t>(buf), n, reinterpret_cast<std::uintptr_t>(stream));
   }
+  void allreduce_sum_u64(uint64_t* buf, size_t n, void* stream) override {
+    GOL_REQUIRE(bool(sum_), "callback transport: no sum callback (census needs one)");
+    py::gil_scoped_acquire gil;
+    sum_(reinterpret_cast<std::uintptr_t>(buf), n, reinterpret_cast<std::uintptr_t>(stream));
+  }
   void barrier() override {
     py::gil_scoped_acquire gil;
     bar_();
@@ -60,6 +66,7 @@ class CallbackTransport final : public Transport {
   ExchangeFn ex_;
   ReduceFn red_;
   BarrierFn bar_;
+  ReduceFn sum_;  // SUM of n 64-bit counts (may be empty: a transport built without it)
 };
 
 py::array_t<uint8_t> to_array(std::vector<uint8_t>&& v, int64_t rows, int64_t cols) {
@@ -167,6 +174,10 @@ PYBIND11_MODULE(_gol, m) {
         return b.supports_boundary(l, parse_rule(rule), parse_boundary(boundary));
       })
       .def("plane_kernel", &Backend::plane_kernel)
+      .def("supports_census", [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary) {
+        return b.supports_census(l, parse_rule(rule), parse_boundary(boundary));
+      })
+      .def("census_kernel", &Backend::census_kernel)
       .def("bind_thread", &Backend::bind_thread);
   m.def("cpu_backend",
         [](int threads, int drift, std::optional<Tuning> tune) {
@@ -221,6 +232,11 @@ PYBIND11_MODULE(_gol, m) {
            [](Transport& t, std::uintptr_t addr, size_t n, std::uintptr_t stream) {
              py::gil_scoped_release rel;
              t.allreduce_max_u32(reinterpret_cast<uint32_t*>(addr), n, reinterpret_cast<void*>(stream));
+           })
+      .def("allreduce_sum_u64",
+           [](Transport& t, std::uintptr_t addr, size_t n, std::uintptr_t stream) {
+             py::gil_scoped_release rel;
+             t.allreduce_sum_u64(reinterpret_cast<uint64_t*>(addr), n, reinterpret_cast<void*>(stream));
            });
   m.def("self_transport", []() { return std::shared_ptr<Transport>(new SelfTransport()); });
   py::class_<ThreadHub, std::shared_ptr<ThreadHub>>(m, "ThreadHub").def(py::init<int>());
@@ -232,9 +248,11 @@ PYBIND11_MODULE(_gol, m) {
         py::arg("hub"), py::arg("rank"), py::arg("backend"), py::arg("tune") = py::none(), py::keep_alive<0, 3>());
   m.def("callback_transport",
         [](int rank, int size, CallbackTransport::ExchangeFn ex, CallbackTransport::ReduceFn red,
-           CallbackTransport::BarrierFn bar) {
-          return std::shared_ptr<Transport>(new CallbackTransport(rank, size, ex, red, bar));
-        });
+           CallbackTransport::BarrierFn bar, CallbackTransport::ReduceFn sum) {
+          return std::shared_ptr<Transport>(new CallbackTransport(rank, size, ex, red, bar, sum));
+        },
+        py::arg("rank"), py::arg("size"), py::arg("exchange"), py::arg("allreduce_max_u32"), py::arg("barrier"),
+        py::arg("allreduce_sum_u64") = CallbackTransport::ReduceFn());
   m.def("rccl_unique_id", []() {
     auto v = rccl_unique_id();
     return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
@@ -262,6 +280,7 @@ PYBIND11_MODULE(_gol, m) {
                     [](EngineConfig& c, const std::string& s) { c.rule = parse_rule(s); })
       .def_property("boundary", [](const EngineConfig& c) { return std::string(boundary_name(c.boundary)); },
                     [](EngineConfig& c, const std::string& s) { c.boundary = parse_boundary(s); })
+      .def_readwrite("census", &EngineConfig::census)
       .def_readwrite("decomp", &EngineConfig::decomp)
       .def_readwrite("gen_limit", &EngineConfig::gen_limit)
       .def_readwrite("check_similarity", &EngineConfig::check_similarity)
@@ -298,7 +317,12 @@ PYBIND11_MODULE(_gol, m) {
       .def_readonly("compute_ms", &RunResult::compute_ms)
       .def_readonly("halo_ms", &RunResult::halo_ms)
       .def_readonly("fill_ms", &RunResult::fill_ms)
-      .def_readonly("allreduce_ms", &RunResult::allreduce_ms);
+      .def_readonly("allreduce_ms", &RunResult::allreduce_ms)
+      .def_property_readonly("population", [](const RunResult& r) {
+        py::array_t<int64_t> a(static_cast<py::ssize_t>(r.population.size()));
+        std::copy(r.population.begin(), r.population.end(), a.mutable_data());
+        return a;
+      });
 
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const EngineConfig& c, std::shared_ptr<Backend> be, std::shared_ptr<Transport> tr) {
@@ -542,7 +566,8 @@ PYBIND11_MODULE(_gol, m) {
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",
         [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, int64_t gen_limit,
-           bool check_similarity, int sim_freq, int threads, const std::string& rule, const std::string& boundary) {
+           bool check_similarity, int sim_freq, int threads, const std::string& rule, const std::string& boundary,
+           bool census) -> py::tuple {
           GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
           int64_t H = a.shape(0), W = a.shape(1);
           std::vector<uint8_t> g(a.data(), a.data() + W * H);
@@ -551,13 +576,16 @@ PYBIND11_MODULE(_gol, m) {
           RefResult r;
           {
             py::gil_scoped_release rel;
-            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl, bd);
+            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl, bd, census);
           }
-          return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W));
+          if (!census) return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W));
+          py::array_t<int64_t> pop(static_cast<py::ssize_t>(r.population.size()));
+          std::copy(r.population.begin(), r.population.end(), pop.mutable_data());
+          return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W), pop);
         },
         py::arg("grid"), py::arg("gen_limit") = 1000, py::arg("check_similarity") = true,
         py::arg("sim_freq") = 3, py::arg("threads") = 1, py::arg("rule") = "B3/S23",
-        py::arg("boundary") = "torus");
+        py::arg("boundary") = "torus", py::arg("census") = false);
 
   // ---- bitop3 / rule emulation (for kernel-level tests) ----
   m.def("rule_words", [](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2,

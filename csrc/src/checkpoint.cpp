@@ -136,6 +136,7 @@ void checkpoint_commit(const std::string& dir, const std::string& grid_path, Che
   if (!rule_is_default(parse_rule(m.rule))) o << "\n \"rule\": \"" << rule_string(parse_rule(m.rule)) << "\",";
   if (parse_boundary(m.boundary) != Boundary::Torus)
     o << "\n \"boundary\": \"" << boundary_name(parse_boundary(m.boundary)) << "\",";
+  if (m.census) o << "\n \"census\": true,";
   o << "\n \"grid\": \"" << m.grid << "\"\n}";
   const std::string tmp = dir + "/meta.json.tmp", fin = dir + "/meta.json";
   {
@@ -188,6 +189,9 @@ CheckpointMeta checkpoint_load(const std::string& dir) {
   if (!rule.empty()) m.rule = rule_string(parse_rule(rule));
   const std::string boundary = json_field(js, "boundary");
   if (!boundary.empty()) m.boundary = boundary_name(parse_boundary(boundary));
+  const std::string census = json_field(js, "census");
+  GOL_REQUIRE(census.empty() || census == "true" || census == "false", "checkpoint '" + dir + "': bad census");
+  m.census = census == "true";
   const std::string grid = json_field(js, "grid");
   if (!grid.empty()) {
     GOL_REQUIRE(checkpoint_grid_name_ok(grid), "checkpoint '" + dir + "': bad grid file name '" + grid +

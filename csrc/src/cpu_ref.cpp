@@ -10,7 +10,8 @@
 namespace gol {
 
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
-                            bool check_similarity, int sim_freq, int threads, Rule rule, Boundary boundary) {
+                            bool check_similarity, int sim_freq, int threads, Rule rule, Boundary boundary,
+                            bool census) {
   GOL_REQUIRE(int64_t(grid.size()) == W * H, "grid size mismatch");
   require_no_b0(rule, rule_string(rule));
   GOL_REQUIRE(sim_freq > 0, "similarity frequency must be positive");
@@ -39,6 +40,7 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
 
   int64_t generation = 1;
   int counter = 0;
+  std::vector<int64_t> population;
   auto t0 = std::chrono::steady_clock::now();
   while (!empty() && generation <= gen_limit) {
     const uint8_t* u = univ;
@@ -74,11 +76,17 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
       counter = 0;
     }
     std::swap(univ, next);
+    if (census) {
+      int64_t live = 0;
+      for (int64_t i = 0; i < W * H; ++i) live += univ[i];
+      population.push_back(live);
+    }
     ++generation;
   }
   auto t1 = std::chrono::steady_clock::now();
   RefResult r;
   r.generations = generation - 1;
+  r.population = std::move(population);
   r.loop_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
   std::copy(univ, univ + W * H, grid.begin());
   return r;

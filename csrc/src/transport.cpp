@@ -123,6 +123,29 @@ void ThreadTransport::allreduce_max_u32(uint32_t* buf, size_t n, void* stream) {
   backend_->copy_h2d(buf, local.data(), n * sizeof(uint32_t));
 }
 
+void ThreadTransport::allreduce_sum_u64(uint64_t* buf, size_t n, void* stream) {
+  if (stream) backend_->synchronize_stream(stream);  // counts written on that stream
+  std::vector<uint64_t> local(n);
+  backend_->copy_d2h(local.data(), buf, n * sizeof(uint64_t));
+  std::unique_lock<std::mutex> lk(hub_->mu);
+  uint64_t gen = hub_->generation;
+  if (hub_->arrived == 0) hub_->red64.assign(n, 0u);
+  GOL_REQUIRE(hub_->red64.size() == n, "thread allreduce: size mismatch");
+  for (size_t i = 0; i < n; ++i) hub_->red64[i] += local[i];
+  if (++hub_->arrived == hub_->size()) {
+    hub_->arrived = 0;
+    ++hub_->generation;
+    hub_->cv.notify_all();
+  } else {
+    hub_->cv.wait(lk, [&] { return hub_->generation != gen; });
+  }
+  local = hub_->red64;
+  lk.unlock();
+  // Everybody must have read `red64` before the next reduction resets it.
+  barrier();
+  backend_->copy_h2d(buf, local.data(), n * sizeof(uint64_t));
+}
+
 void ThreadTransport::barrier() {
   std::unique_lock<std::mutex> lk(hub_->mu);
   uint64_t gen = hub_->generation;

@@ -135,6 +135,11 @@ class RcclTransport final : public Transport {
     NCCL_CHECK(ncclAllReduce(buf, buf, n, ncclUint32, ncclMax, flags_comm_ ? flags_comm_ : comm_,
                              static_cast<hipStream_t>(stream)));
   }
+  // On the exchange communicator: once per run, in stream order with the halos.
+  void allreduce_sum_u64(uint64_t* buf, size_t n, void* stream) override {
+    DeviceScope on(dev_);
+    NCCL_CHECK(ncclAllReduce(buf, buf, n, ncclUint64, ncclSum, comm_, static_cast<hipStream_t>(stream)));
+  }
   bool side_reduce() const override { return flags_comm_ != nullptr; }
   int comm_count() const override {
     int n = 0;

@@ -61,6 +61,8 @@ struct Options {
   bool rule_set = false;
   Boundary boundary = Boundary::Torus;  // --boundary
   bool boundary_set = false;
+  std::string census;  // --census PATH ("": off)
+  bool census_on = false;  // --census, or a resumed checkpoint's setting
   std::string decomp = "auto";
   std::string comm = "auto";  // auto | thread | rccl (in-process ranks)
   std::string output;  // default: the matching reference build's file (see default_output)
@@ -99,6 +101,9 @@ struct Options {
                "  --boundary torus|dead       what lies beyond the grid's edge: the torus wraps (default);\n"
                "                              dead = a bounded plane whose outside is dead in every\n"
                "                              generation (hip engine: B3/S23 only; no lds kernels, graphs)\n"
+               "  --census PATH               count the live cells of every generation inside the temporal\n"
+               "                              blocks and write 'generation,population' lines to PATH (hip\n"
+               "                              engine: B3/S23 on the torus; no lds kernels, graphs)\n"
                "  --gens N                    GEN_LIMIT (default 1000)\n"
                "  --sim-freq F                SIMILARITY_FREQUENCY (default 3)\n"
                "  --no-similarity             disable the similarity check\n"
@@ -152,6 +157,7 @@ Options parse(int argc, char** argv) {
     }
     else if (a == "--rule") o.rule = parse_rule(next()), o.rule_set = true;
     else if (a == "--boundary") o.boundary = parse_boundary(next()), o.boundary_set = true;
+    else if (a == "--census") o.census = next(), o.census_on = true;
     else if (a == "--decomp") o.decomp = next();
     else if (a == "--comm") o.comm = next();
     else if (a == "--gens") o.gens = std::atoll(next().c_str()), o.gens_set = true;
@@ -221,6 +227,8 @@ Options parse(int argc, char** argv) {
       throw Error("--resume: checkpoint was taken with --boundary " + m.boundary + ", not " +
                   boundary_name(o.boundary));
     o.boundary = ck_boundary;
+    // A census is per run: --census counts the resumed run whether or not the first one did.
+    o.census_on = o.census_on || m.census;
     o.W = m.W;
     o.H = m.H;
     o.input = checkpoint_grid_path(o.resume);
@@ -299,7 +307,8 @@ int run(const Options& o) {
     }
     read_ms = ms_since(t0);
     RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule,
-                                     o.boundary);
+                                     o.boundary, o.census_on);
+    res.population = rr.population;
     res.generations = rr.generations;
     res.loop_ms = rr.loop_ms;
     res.executed = rr.generations;
@@ -317,6 +326,7 @@ int run(const Options& o) {
     cfg.layout = layout;
     cfg.rule = o.rule;
     cfg.boundary = o.boundary;
+    cfg.census = o.census_on;
     cfg.decomp = o.decomp;
     cfg.gen_limit = o.gens;
     cfg.check_similarity = o.similarity;
@@ -433,6 +443,8 @@ int run(const Options& o) {
       total.exchanges += results[0].exchanges;
       total.polls += results[0].polls;
       total.kernel_launches += results[0].kernel_launches;
+      // The chunks' series concatenate to the whole run's (every rank holds the global sum).
+      total.population.insert(total.population.end(), results[0].population.begin(), results[0].population.end());
       // Per-phase device times: the slowest rank's, like loop_ms.
       for (auto& rr : results) {
         total.phase_timed = total.phase_timed || rr.phase_timed;
@@ -473,6 +485,7 @@ int run(const Options& o) {
         m.layout = layout_name(layout);
         m.rule = rule_string(o.rule);
         m.boundary = boundary_name(o.boundary);
+        m.census = o.census_on;
         // Fault injection (tests): die after the N-th checkpoint's tiles are
         // written, before it is committed.
         if (const int c = o.tune.i("fault_checkpoint_crash"))
@@ -533,8 +546,21 @@ int run(const Options& o) {
         << ", \"overlap_trial_ms_trigger\": " << engines[0]->trial_ms_trigger()
         << ", \"phase_timed\": " << (res.phase_timed ? "true" : "false") << ", \"compute_ms\": " << res.compute_ms
         << ", \"halo_ms\": " << res.halo_ms << ", \"fill_ms\": " << res.fill_ms
-        << ", \"allreduce_ms\": " << res.allreduce_ms << "}\n";
+        << ", \"allreduce_ms\": " << res.allreduce_ms;
+      if (o.census_on) {
+        f << ", \"census\": true, \"population\": [";
+        for (size_t i = 0; i < res.population.size(); ++i) f << (i ? ", " : "") << res.population[i];
+        f << "]";
+      }
+      f << "}\n";
     }
+  }
+  // --census PATH: generation,population lines, one per generation of the run.
+  if (!o.census.empty()) {
+    std::ofstream f(o.census);
+    GOL_REQUIRE(f.good(), "--census: cannot write '" + o.census + "'");
+    for (size_t i = 0; i < res.population.size(); ++i)
+      f << o.start_gen + 1 + int64_t(i) << "," << res.population[i] << "\n";
   }
 
   // stdout contract of the matching reference build.

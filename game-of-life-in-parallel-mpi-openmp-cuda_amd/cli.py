@@ -36,6 +36,10 @@ def parse_args(argv=None):
     p.add_argument("--boundary", default=None, choices=["torus", "dead"],
                    help="what lies beyond the grid's edge: torus wraps (default); dead = a bounded plane whose "
                         "outside is dead in every generation (hip engine: B3/S23 only, no lds kernels, no graphs)")
+    p.add_argument("--census", default=None, metavar="PATH",
+                   help="count the live cells of every generation inside the temporal blocks and write "
+                        "'generation,population' lines to PATH, one per generation (hip engine: B3/S23 on the torus, "
+                        "no lds kernels, no graphs)")
     p.add_argument("--gens", type=int, default=1000, help="GEN_LIMIT")
     p.add_argument("--sim-freq", type=int, default=None, help="SIMILARITY_FREQUENCY (default 3)")
     p.add_argument("--no-similarity", action="store_true")
@@ -81,6 +85,13 @@ def parse_args(argv=None):
     return a
 
 
+def write_census(path: str, g0: int, population) -> None:
+    """``generation,population`` lines, one per generation after ``g0``."""
+    with open(path, "w") as f:
+        for i, v in enumerate(population):
+            f.write(f"{g0 + 1 + i},{int(v)}\n")
+
+
 def print_tuning_keys() -> None:
     from ._native import native  # noqa: PLC0415
 
@@ -115,8 +126,11 @@ def main(argv=None) -> int:
         t0 = time.perf_counter()
         grid = random_grid(a.width, a.height, seed, density) if a.random else read_grid(a.input_file, a.width, a.height)
         read_ms = (time.perf_counter() - t0) * 1e3
-        out, gens, ms = reference_run(np.asarray(grid), a.gens, not a.no_similarity, a.sim_freq, max(1, a.threads),
-                                      rule=rule, boundary=boundary)
+        out, gens, ms, *pop = reference_run(np.asarray(grid), a.gens, not a.no_similarity, a.sim_freq,
+                                            max(1, a.threads), rule=rule, boundary=boundary,
+                                            census=a.census is not None)
+        if a.census is not None:
+            write_census(a.census, 0, pop[0])
         t1 = time.perf_counter()
         if a.output != "none":
             write_grid(a.output, out)
@@ -147,7 +161,8 @@ def main(argv=None) -> int:
     cfg = LifeConfig(a.width, a.height, gen_limit=a.gens, check_similarity=not a.no_similarity,
                      sim_freq=a.sim_freq, layout=a.layout, decomp=a.decomp, tmax=a.tmax,
                      epoch=a.epoch, poll_gens=a.poll, overlap=a.overlap, graphs=a.graphs,
-                     u8_compute=a.u8_compute, tune=tune, rule=rule, boundary=boundary)
+                     u8_compute=a.u8_compute, tune=tune, rule=rule, boundary=boundary,
+                     census=a.census is not None)
     src = a.input_file
     if a.resume:
         from .utils.checkpoint import load_checkpoint  # noqa: PLC0415
@@ -161,11 +176,14 @@ def main(argv=None) -> int:
         if a.sim_freq_given and not a.no_similarity and a.sim_freq != cfg.sim_freq:
             raise SystemExit(f"--resume: checkpoint was taken with --sim-freq {cfg.sim_freq}; resuming with "
                              f"--sim-freq {a.sim_freq} would shift the similarity checks")
+        # A census is per run: --census counts the resumed run whether or not the first one did.
+        cfg.census = cfg.census or a.census is not None
         src = str(grid_path)
     sim = Simulation(cfg, transport=transport, backend=backend)
     # Opt-in only: the event pairs would sit inside the loop that loop_ms and
     # the reference-style timing line report.
     sim.phase_timing = bool(a.phase_timing)
+    g0 = sim.generation
     t0 = time.perf_counter()
     if a.random is not None and not a.resume:
         sim.init_random(seed, density)
@@ -201,6 +219,10 @@ def main(argv=None) -> int:
         sys.stdout.write(stdout_lines(a.style, rep.generations, rep.loop_ms, read_ms, write_ms, world))
         sys.stdout.flush()
         rec = rep.as_dict()
+        if cfg.census:
+            rec["population"] = [int(v) for v in rep.population]
+        if a.census is not None:
+            write_census(a.census, g0, rep.population)
         rec.update(sim.describe())
         rec.update({"read_ms": read_ms, "write_ms": write_ms, "width": a.width, "height": a.height})
         write_json(a.metrics_json, rec)

@@ -39,6 +39,7 @@ class LifeConfig:
     layout: str = "auto"        # auto | bits | u8
     rule: str = "B3/S23"        # Life-like rule: B<digits>/S<digits> or a name of gol_amd.RULES (no B0)
     boundary: str = "torus"     # torus | dead: the grid wraps, or is a bounded plane whose outside is always dead
+    census: bool = False        # every run also returns the live cells of every generation (RunReport.population)
     decomp: str = "auto"        # auto | PxQ
     tmax: int = 0               # generations per kernel launch (0 = the backend's choice: bits 12 adder /
                                 # 16 DPP; u8 32 / 24 / 16 by tile size)
@@ -75,6 +76,7 @@ class LifeConfig:
         c.layout = C.Layout.Bits if self.resolved_layout() == "bits" else C.Layout.U8
         c.rule = str(self.rule)
         c.boundary = str(self.boundary)
+        c.census = bool(self.census)
         c.decomp = self.decomp
         c.gen_limit = int(self.gen_limit)
         c.check_similarity = bool(self.check_similarity)
@@ -174,13 +176,16 @@ class RunReport:
     halo_ms: float = 0.0
     fill_ms: float = 0.0
     allreduce_ms: float = 0.0
+    # LifeConfig.census: live cells of the whole grid (summed over ranks) at every generation
+    # the run advanced through, entry i for generation g0 + 1 + i; empty when the census is off.
+    population: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, dtype=np.int64), compare=False)
 
     @property
     def cell_updates_per_s(self) -> float:
         return self.cells * self.executed / (self.loop_ms * 1e-3) if self.loop_ms > 0 else 0.0
 
     def as_dict(self) -> dict[str, Any]:
-        d = dataclasses.asdict(self)
+        d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if f.name != "population"}
         d["cell_updates_per_s"] = self.cell_updates_per_s
         return d
 
@@ -247,7 +252,8 @@ class Simulation:
         g = self._eng.compute_geom  # the tile the temporal blocks run on (halos)
         return {"backend": self.backend.name(), "transport": self.transport.name(),
                 "layout": self.config.resolved_layout(), "rule": self._eng.config.rule,
-                "boundary": self._eng.config.boundary, "decomp": d.describe(),
+                "boundary": self._eng.config.boundary, "census": bool(self._eng.config.census),
+                "decomp": d.describe(),
                 "rank": self.rank, "ranks": d.nranks(), "tile_rows": g.H, "tile_cols": g.W,
                 "halo_rows": g.Dv, "halo_words": g.hw, "tmax": self._eng.tmax,
                 "epoch": self._eng.epoch_depth, "pitch": self._eng.geom.pitch, "overlap": self._eng.overlap(),
@@ -326,6 +332,14 @@ class Simulation:
             pk = self.backend.plane_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
             if pk:
                 parts.append(f"plane kernels: {pk}")
+        if e.config.census:
+            # The census kernels: the DPP window whatever xlane asks for, T <= 16 in both layouts;
+            # the row ring and wrapped column reads stay (their blocks cover the owned cells once).
+            parts.append("census (per-generation live-cell counts fused into the temporal blocks; no linked or "
+                         "chained launches, no skipping, no lazy tail, no folded strip)")
+            ck = self.backend.census_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
+            if ck:
+                parts.append(f"census kernels: {ck}")
         return ", ".join(parts)
 
     # -- state -----------------------------------------------------------
@@ -364,7 +378,7 @@ class Simulation:
                         graph_launches=r.graph_launches, halo_bytes=r.halo_bytes,
                         linked_launches=r.linked_launches, phase_timed=r.phase_timed,
                         compute_ms=r.compute_ms, halo_ms=r.halo_ms, fill_ms=r.fill_ms,
-                        allreduce_ms=r.allreduce_ms)
+                        allreduce_ms=r.allreduce_ms, population=np.asarray(r.population, dtype=np.int64))
         self.last_report = rep
         return rep
 
@@ -392,14 +406,18 @@ def simulate(grid: np.ndarray, gens: int, engine: str = "auto", layout: str = "a
 
 def reference_run(grid: np.ndarray, gen_limit: int = 1000, check_similarity: bool = True,
                   sim_freq: int = 3, threads: int = 1, rule: str = DEFAULT_RULE,
-                  boundary: str = DEFAULT_BOUNDARY) -> tuple[np.ndarray, int, float]:
+                  boundary: str = DEFAULT_BOUNDARY, census: bool = False):
     """Exact eager serial loop of src/game.c (native), under any Life-like
     ``rule`` without B0, on the torus or (``boundary="dead"``) the bounded
-    plane.  Returns (grid, gens, ms)."""
-    gens, ms, out = native().cpu_reference_run(np.ascontiguousarray(grid, dtype=np.uint8), int(gen_limit),
-                                               bool(check_similarity), int(sim_freq), int(threads), str(rule),
-                                               str(boundary))
-    return out, int(gens), float(ms)
+    plane.  Returns (grid, gens, ms); with ``census=True`` (grid, gens, ms,
+    population), population[i] the live cells of generation 1 + i (int64,
+    ``gens`` entries)."""
+    r = native().cpu_reference_run(np.ascontiguousarray(grid, dtype=np.uint8), int(gen_limit),
+                                   bool(check_similarity), int(sim_freq), int(threads), str(rule),
+                                   str(boundary), bool(census))
+    if census:
+        return r[2], int(r[0]), float(r[1]), np.asarray(r[3], dtype=np.int64)
+    return r[2], int(r[0]), float(r[1])
 
 
 def timed(fn, *a, **kw):

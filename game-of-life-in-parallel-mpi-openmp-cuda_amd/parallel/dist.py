@@ -102,9 +102,9 @@ def tensor_view(ptr: int, nbytes: int, on_device: bool, dtype: str = "u1"):
     import torch  # noqa: PLC0415
 
     if on_device:
-        typestr, item = ("|u1", 1) if dtype == "u1" else ("<i4", 4)
+        typestr, item = {"u1": ("|u1", 1), "i4": ("<i4", 4), "i8": ("<i8", 8)}[dtype]
         return torch.as_tensor(_DeviceBuf(ptr, nbytes, typestr, item), device="cuda")
-    arr = _host_view(ptr, nbytes, np.uint8 if dtype == "u1" else np.int32)
+    arr = _host_view(ptr, nbytes, {"u1": np.uint8, "i4": np.int32, "i8": np.int64}[dtype])
     return torch.from_numpy(arr)
 
 
@@ -139,10 +139,16 @@ def torch_transport(backend_obj, group=None):
             if not on_dev:
                 return
 
+    def allreduce_sum(addr, n, stream_ptr):
+        # The census series: 64-bit counts, far below 2^63, summed as int64.
+        with _stream_ctx(stream_ptr):
+            t = tensor_view(addr, 8 * n, on_dev, dtype="i8")
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
     def barrier():
         dist.barrier(group=group)
 
-    return native().callback_transport(rank, world, exchange, allreduce, barrier)
+    return native().callback_transport(rank, world, exchange, allreduce, barrier, allreduce_sum)
 
 
 def rccl_transport(device: int, group=None, tune=None):

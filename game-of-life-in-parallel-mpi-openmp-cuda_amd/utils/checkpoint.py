@@ -25,6 +25,8 @@ import re
 from pathlib import Path
 from typing import Optional
 
+import numpy as np
+
 from ..models.life import DEFAULT_BOUNDARY, DEFAULT_RULE, LifeConfig, RunReport, Simulation, parse_rule
 from .termination import reported_generations, sim_phase_at
 
@@ -105,6 +107,10 @@ def save_checkpoint(sim: Simulation, directory: str, is_root: bool = True, barri
     # "boundary" likewise, only when it is not the torus (a missing key means the torus).
     if cfg.boundary != DEFAULT_BOUNDARY:
         meta = {k: v for k, v in meta.items() if k != "grid"} | {"boundary": _boundary(cfg.boundary), "grid": name}
+    # "census" likewise, only when it is on (a missing key means off).  The series itself is
+    # per run and is not checkpointed.
+    if cfg.census:
+        meta = {k: v for k, v in meta.items() if k != "grid"} | {"census": True, "grid": name}
     grid = d / name
     if is_root:
         from .io import create_text_file  # noqa: PLC0415
@@ -149,7 +155,8 @@ def load_checkpoint(directory: str, **overrides) -> tuple[LifeConfig, Path]:
                      check_similarity=meta["check_similarity"], sim_freq=meta["sim_freq"],
                      layout=meta.get("layout", "auto"), start_gen=meta["generation"],
                      sim_phase=meta["sim_phase"], rule=parse_rule(meta.get("rule", DEFAULT_RULE)),
-                     boundary=_boundary(meta.get("boundary", DEFAULT_BOUNDARY)))
+                     boundary=_boundary(meta.get("boundary", DEFAULT_BOUNDARY)),
+                     census=bool(meta.get("census", False)))
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg, d / _meta_grid(meta, d)
@@ -162,6 +169,7 @@ def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], 
     limit = cfg.gen_limit
     eng = sim.native_engine
     total_ms, executed, exch, polls, launches = 0.0, 0, 0, 0, 0
+    population = []  # LifeConfig.census: the chunks' series concatenate to the whole run's
     while True:
         target = min(limit, sim.generation + every) if every > 0 else limit
         r = eng.run_until(target)
@@ -170,10 +178,11 @@ def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], 
         exch += r.exchanges
         polls += r.polls
         launches += r.kernel_launches
+        population.append(np.asarray(r.population, dtype=np.int64))
         if r.first_unchanged >= 0 or sim.generation >= limit:
             gens, reason = reported_generations(r.first_unchanged, r.extinct, limit, cfg.start_gen,
                                                 cfg.check_similarity, cfg.sim_freq, cfg.sim_phase)
             return RunReport(gens, executed, reason, total_ms, r.first_unchanged, r.extinct, exch,
-                             polls, launches, cfg.width * cfg.height)
+                             polls, launches, cfg.width * cfg.height, population=np.concatenate(population))
         if directory:
             save_checkpoint(sim, directory, is_root, barrier)
