@@ -159,8 +159,9 @@ class Backend {
   };
   virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req,
                                      Rule /*rule*/ = Rule{}, Boundary boundary = Boundary::Torus,
-                                     bool /*census*/ = false) const {
-    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && boundary == Boundary::Torus};
+                                     bool /*census*/ = false, bool fingerprint = false) const {
+    // A fingerprint weighs every cell by its column: no drifting frame.
+    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && boundary == Boundary::Torus && !fingerprint};
   }
   // Quiet-tile skipping (BlockArgs::quiet, gol/quiet.hpp).  quiet_mode(): the
   // backend's tuning quiet_skip (0: it has no such kernel or it is off, 1
@@ -225,6 +226,13 @@ class Backend {
   // Description of the kernels that run a census engine ("" where the backend
   // has one kind only).
   virtual std::string census_kernel(Layout) const { return ""; }
+  // The same trio for BlockArgs::fingerprint (the per-generation grid
+  // fingerprint, gol/fingerprint.hpp); `census`: the engine also runs a census.
+  virtual bool supports_fingerprint(Layout, Rule, Boundary, bool /*census*/) const { return false; }
+  virtual std::string unsupported_fingerprint(Layout, Rule, Boundary, bool /*census*/) const {
+    return "backend " + name() + " does not run fingerprint=1";
+  }
+  virtual std::string fingerprint_kernel(Layout) const { return ""; }
   // Row ring (single-rank torus): a tile whose top Dv halo rows are a second
   // virtual mapping of its last Dv owned rows and whose bottom halo rows map
   // its first ones, so the periodic row halos are always valid and never
@@ -250,6 +258,19 @@ class Backend {
   virtual void alive_any(const void* buf, const TileGeom& g, uint32_t* flag) = 0;
   // Count of live owned cells (synchronous, for diagnostics/tests).
   virtual int64_t alive_count(const void* buf, const TileGeom& g) = 0;
+  // Fingerprint share of the tile's owned cells (gol/fingerprint.hpp) added to
+  // *out64 (backend memory, zeroed by the caller; stream-ordered): owned row 0
+  // is global row global_row0, the first owned cell global cell global_col0 (a
+  // backend may need it to be a multiple of 32: supports_fingerprint's caller
+  // checks the decomposition).
+  virtual void fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
+                           uint64_t* out64) = 0;
+  // The owned rows of tile `src` into `dst`, a buffer of g.bytes() bytes
+  // (stream-ordered; src may be a row ring): Engine::find_cycle's copy.
+  virtual void copy_owned_rows(void* dst, const void* src, const TileGeom& g) = 0;
+  // *flag (backend memory, zeroed by the caller; stream-ordered) = 1 if any
+  // owned cell of two tiles of geometry g differs.
+  virtual void tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) = 0;
   // Host <-> tile conversion: `cells` is an H x W array of bytes (ld = row
   // stride); load treats byte == '1' or byte == 1 as alive; store writes
   // '0'/'1' when ascii else 0/1.

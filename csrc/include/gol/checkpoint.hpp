@@ -47,6 +47,8 @@ struct CheckpointMeta {
   // on; a missing key means off.  The series itself is per run and is not
   // checkpointed.
   bool census = false;
+  // EngineConfig::fingerprint, likewise: a "fingerprint" key only when on.
+  bool fingerprint = false;
   std::string grid = "grid.txt";  // grid file name inside the checkpoint directory
 };
 

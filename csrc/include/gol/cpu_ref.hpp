@@ -17,6 +17,7 @@ struct RefResult {
   int64_t generations = 0;
   double loop_ms = 0;
   std::vector<int64_t> population;  // cpu_reference_run(..., census = true)
+  std::vector<uint64_t> fingerprint;  // cpu_reference_run(..., fingerprint = true)
 };
 
 // `grid` holds H*W cells (0/1 or ASCII) and is overwritten with the final
@@ -28,8 +29,10 @@ struct RefResult {
 // bounded plane) instead of wrapping around the torus.
 // `census`: RefResult::population receives the live cells of every generation
 // the loop advanced through (entry i: generation 1 + i; `generations` entries).
+// `fingerprint`: RefResult::fingerprint receives the grid fingerprint
+// (gol/fingerprint.hpp) of the same generations.
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
                             bool check_similarity, int sim_freq, int threads, Rule rule = Rule{},
-                            Boundary boundary = Boundary::Torus, bool census = false);
+                            Boundary boundary = Boundary::Torus, bool census = false, bool fingerprint = false);
 
 }  // namespace gol

@@ -46,6 +46,13 @@ struct EngineConfig {
   // or chained launches, no quiet-tile skipping, no lazy tail, no boundary
   // trigger and no graphs.
   bool census = false;
+  // Grid fingerprint (gol/fingerprint.hpp): every run also returns a
+  // position-dependent 64-bit fingerprint of every generation it advanced
+  // through (RunResult::fingerprint), accumulated inside the temporal blocks
+  // (BlockArgs::fingerprint) and summed over ranks modulo 2^64; the series
+  // Engine::find_cycle searches.  Off by default, and nothing changes when
+  // off.  A fingerprint engine is scheduled exactly like a census engine.
+  bool fingerprint = false;
   std::string decomp = "auto";     // "auto" or "PxQ"
   int64_t gen_limit = 1000;        // GEN_LIMIT (src/game.c:6)
   bool check_similarity = true;    // CHECK_SIMILARITY (src/game.c:8)
@@ -142,6 +149,32 @@ struct RunResult {
   // over ranks, on every rank) at generation g0 + 1 + i, g0 the generation the
   // run started at; exactly Engine::generation() - g0 entries.  Empty when off.
   std::vector<int64_t> population;
+  // EngineConfig::fingerprint: entry i is the fingerprint of the whole grid at
+  // generation g0 + 1 + i (on every rank); Engine::generation() - g0 entries.
+  // Empty when off.
+  std::vector<uint64_t> fingerprint;
+};
+
+// Engine::find_cycle's result.  `period` and `generation` are exact: confirmed
+// by comparing the cells of two generations.  `repeats_from` is fingerprint
+// evidence.
+struct CycleResult {
+  int64_t period = 0;       // the cycle's minimal period; 0: none found
+  // A generation confirmed to lie on the cycle (grid(generation) ==
+  // grid(generation - period)); where the engine stops: Engine::generation().
+  int64_t generation = 0;
+  // The earliest generation since the call began from which the fingerprints
+  // repeat with `period`: a lower bound on the generation the grid entered the
+  // cycle at, and equal to it unless two different grids of the transient
+  // collide (or the cycle was entered before the call).  -1 with period 0.
+  int64_t repeats_from = -1;
+  int64_t confirmations = 0;     // exact comparisons that found the repeat (0 or 1)
+  int64_t false_candidates = 0;  // candidate periods that an exact comparison rejected
+  std::string stop_reason = "limit";  // cycle | limit | extinction
+  double loop_ms = 0;            // wall time of the call
+  // The fingerprints of the generations the call advanced through (entry i:
+  // generation g0 + 1 + i, g0 where the call began), as RunResult::fingerprint.
+  std::vector<uint64_t> fingerprint;
 };
 
 // The reference's "Generations:" value of a run over (start_gen, limit] whose
@@ -262,6 +295,10 @@ class Engine {
   void store_rows(uint8_t* cells, int64_t ld, int64_t r0, int64_t n, bool ascii);
   void init_random(uint64_t seed, double density);
   int64_t alive_count();  // local owned cells
+  // Fingerprint of the current grid (gol/fingerprint.hpp), summed over ranks:
+  // every rank calls it.  Any engine, whatever EngineConfig::fingerprint says
+  // (the HIP backend needs tiles that start on a multiple of 32 columns).
+  uint64_t fingerprint();
 
   // Runs from the current generation up to config().gen_limit with the
   // reference's termination semantics.
@@ -272,6 +309,18 @@ class Engine {
   // Runs exactly n more generations (termination flags still recorded, but
   // no early stop): the bench path.
   RunResult advance(int64_t n);
+  // Runs until the grid is confirmed to repeat with a period <= max_period, or
+  // to generation max_gens (an absolute generation, like run_until's limit;
+  // not bounded by gen_limit).  A loop above the run: chunks of `chunk`
+  // generations (0: 256), then a search of the fingerprint series since the
+  // call began for periods p whose last p generations all satisfy
+  // F(g) == F(g - p); the candidates and their divisors are then confirmed
+  // exactly, ascending, against a copy of the grid, so the first that matches
+  // is the minimal period.  A chunk the change flags stop early is an exact
+  // period 1 (stop_reason extinction if the grid is empty).  Needs
+  // EngineConfig::fingerprint; every rank calls it and takes the same
+  // decisions (the series is global).
+  CycleResult find_cycle(int64_t max_gens, int max_period, int64_t chunk = 0);
 
   // Exchange halos of the current buffer (exposed for tests).
   void halo_exchange();
@@ -458,6 +507,14 @@ class Engine {
   // filling it (launches outside a run - step_block - count nothing).
   Owned<uint64_t> census_;
   bool census_run_ = false;
+  // EngineConfig::fingerprint: the same for the fingerprint series; the device
+  // word of fingerprint(); find_cycle's copy of the state tile.
+  Owned<uint64_t> fprint_;
+  bool fprint_run_ = false;
+  Owned<uint64_t> fp_dev_;
+  Owned<> snap_;
+  size_t snap_bytes_ = 0;
+  bool differs_from_snapshot();
   bool drift_ok_ = false;   // whole-width tile of 32-cell words on a drifting backend
   bool cols_filled_ = true; // column halos kept valid by fills (false: the backend wraps column reads)
   bool rows_wrapped_ = false; // single-rank torus read modulo its rows (no fills at all)

@@ -126,6 +126,14 @@ struct BlockArgs {
   // live cells of the tile's owned rows and cells at each of its generations
   // L = 1..T.  Null: no census.  Never set together with link, quiet or gen_dev.
   uint64_t* census = nullptr;
+  // Fingerprint (EngineConfig::fingerprint; gol/fingerprint.hpp): a window of
+  // 64-bit values addressed like `census`; the block adds the fingerprint share
+  // of the tile's owned rows and cells at each of its generations L = 1..T.
+  // global_row0 / global_col0: the global row and cell of the tile's first
+  // owned row and cell.  Null: no fingerprint.  Never set together with link,
+  // quiet or gen_dev; a HIP launch takes a census or a fingerprint, not both.
+  uint64_t* fingerprint = nullptr;
+  int64_t global_row0 = 0, global_col0 = 0;
 };
 
 }  // namespace gol

@@ -82,6 +82,14 @@ std::string life_block_census_variant(Layout layout, const LifeTuning& tune) {
          (tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)";
 }
 
+std::string life_block_fprint_variant(Layout layout, const LifeTuning& tune) {
+  const bool grouped = tune.group != 0;
+  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp fingerprint" +
+         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window with the fingerprint)" : "") +
+         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "") +
+         (tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)";
+}
+
 int life_block_max_T(Layout layout, const LifeTuning& tune) {
   if (layout == Layout::U8 && tune.u8_lds) return tune.lds_T;
   // Register budget for 2 waves/SIMD (<= 256 VGPRs): T <= 16 (one word per lane).
@@ -164,11 +172,35 @@ LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const
     // A wave's count of one generation stays below 2^31 (64 lanes x 32 cells x rows).
     GOL_REQUIRE(rows + 2 * a.T < (int64_t(1) << 20), "life_block: census needs blocks of fewer than 2^20 rows");
     GOL_REQUIRE(a.gen_base >= a.flags_base, "life_block: census block before its window");
+    GOL_REQUIRE(!a.fingerprint, "life_block: census and fingerprint in one launch");
     p.link_ring_rows = 0;
     p.grid_row_lo = int(g.Dv);
     p.grid_row_hi = int(g.Dv + g.H);
     p.census = reinterpret_cast<unsigned long long*>(a.census) + (a.gen_base + 1 - a.flags_base);
     return (g.layout == Layout::U8 ? launch_census_u8_dpp : launch_census_bits_dpp)(p, rows, a.T, tune, ctx, stream);
+  }
+  if (a.fingerprint) {
+    // The fingerprint: lb::FingerprintIO kernels, launched like the census
+    // kernels above.  Rows and words travel in 32 bits; the tile's first owned
+    // column is a word boundary of the global grid (the engine refuses a byte
+    // decomposition where it is not).
+    GOL_REQUIRE(rule_is_default(a.rule), "life_block: fingerprint runs B3/S23 only on the HIP engine");
+    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: fingerprint with u8_kernel=lds");
+    GOL_REQUIRE(!a.allow_drift && !a.wrap_rows && !a.link && !a.quiet && !a.gen_dev,
+                "life_block: fingerprint with a launch option it does not run with");
+    GOL_REQUIRE(a.T <= 16, "life_block: fingerprint kernels run temporal blocks of at most 16 generations");
+    GOL_REQUIRE(a.gen_base >= a.flags_base, "life_block: fingerprint block before its window");
+    GOL_REQUIRE(a.global_col0 % 32 == 0, "life_block: fingerprint tile off the global word grid");
+    GOL_REQUIRE(a.global_row0 >= 0 && a.global_row0 + g.R() < (int64_t(1) << 31) &&
+                    a.global_col0 / 32 + g.Wp() < (int64_t(1) << 31),
+                "life_block: fingerprint needs global rows and words below 2^31");
+    p.link_ring_rows = 0;
+    p.grid_row_lo = int(g.Dv);
+    p.grid_row_hi = int(g.Dv + g.H);
+    p.fingerprint = reinterpret_cast<unsigned long long*>(a.fingerprint) + (a.gen_base + 1 - a.flags_base);
+    p.fp_row0 = int(a.global_row0 - g.Dv);
+    p.fp_word0 = int(a.global_col0 / 32);
+    return (g.layout == Layout::U8 ? launch_fprint_u8_dpp : launch_fprint_bits_dpp)(p, rows, a.T, tune, ctx, stream);
   }
   int x = tune.xlane == kXlaneAdd || tune.xlane == kXlaneAuto ? tune.xlane : kXlaneDpp;
   // Any rule but B3/S23: the kernels compiled from life_rules.def.

@@ -40,6 +40,7 @@
 #include <algorithm>
 
 #include "gol/common.hpp"
+#include "gol/fingerprint.hpp"
 #include "gol/tile.hpp"
 #include "life_kernels.hpp"
 
@@ -367,6 +368,7 @@ struct BitsIO {
   using Rule = Rule_;
   using Edge = Torus;  // PlaneIO
   static constexpr bool kCensus = false;  // CensusIO
+  static constexpr bool kFprint = false;  // FingerprintIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = 1;  // halo lanes per wave side
   static constexpr bool kLinked = false;  // Sc1IO
@@ -411,6 +413,7 @@ struct U8IO {
   using Rule = Rule_;
   using Edge = Torus;  // PlaneIO
   static constexpr bool kCensus = false;  // CensusIO
+  static constexpr bool kFprint = false;  // FingerprintIO
   static constexpr int W = W_, XL = XL_;
   static constexpr int kHalo = HALO_;  // halo lanes per wave side (2: passes deeper than 32)
   static constexpr bool kLinked = false;  // Sc1IO
@@ -535,6 +538,44 @@ struct CensusState<true, T, W> {
   __device__ __forceinline__ uint32_t row_mask(int k, int L) const { return uint32_t(rel + k - L) < rows ? ~0u : 0u; }
 };
 
+// Storage layout of a fingerprint launch (BlockArgs::fingerprint): IO whose
+// level bodies also accumulate the fingerprint share of every generation of the
+// block (FprintState).  A wrapper like CensusIO; a launch is one or the other.
+template <class IO>
+struct FingerprintIO : IO {
+  static constexpr bool kFprint = true;
+};
+
+// A fused per-generation reduction beside the change flags (census or
+// fingerprint): such a launch is never folded, linked, chained or deep.
+template <class IO>
+inline constexpr bool kSeries = IO::kCensus || IO::kFprint;
+
+// Fingerprint (gol/fingerprint.hpp): the census's reduction, weighted by where
+// each cell is.  Every level body adds word * r(y) to a per-level, per-lane
+// 64-bit sum for the words the census would count (the same fm / rel / rows
+// window: the rows the wave or group evaluates completely, clipped to the
+// owned rows).  The row key r(y) of the level row's global row y is
+// wave-uniform: a scalar multiply chain on the SALU (row_key).  The column key
+// A(j) of the lane's global word is applied once per lane and level at the end
+// of the wave (fprint_wave_sums).  Sums are modulo 2^64, so nothing overflows.
+template <bool On, int T, int W>
+struct FprintState {};
+template <int T, int W>
+struct FprintState<true, T, W> {
+  uint64_t acc[T][W];  // [L]: sum of word * r(y) over the counted level-(L+1) rows of the lane's word i
+  uint32_t fm[W];      // LaneCols::fmask
+  int gword;           // global word index of the lane's word 0
+  int rel;             // the wave's first input row (sweep step 0) minus lo
+  uint32_t rows;       // hi - lo (0: the wave counts nothing)
+  int y0;              // global row of the wave's first input row
+  __device__ __forceinline__ uint32_t row_mask(int k, int L) const { return uint32_t(rel + k - L) < rows ? ~0u : 0u; }
+  // r(y) of the level-L row of sweep step k (wave-uniform; any value where row_mask is 0).
+  __device__ __forceinline__ uint32_t row_key(int k, int L) const {
+    return fingerprint_row_key(uint32_t(__builtin_amdgcn_readfirstlane(y0 + k - L)));
+  }
+};
+
 // Row reader with a 3-deep register prefetch: the row for step k sits in
 // slot k % 3 and is replaced by the load for step k + 3 when consumed.
 // Rows in flight per wave: sets of 3 (the window's slots), the oldest set
@@ -581,15 +622,16 @@ struct RowReader {
 
 // Per-wave state.  Level L (0..T-1) keeps, for its last three rows (slot =
 // row index mod 3), the horizontal sums h0/h1 and the cells themselves.
-template <int T, int W, class Edge = Torus, bool Census = false>
+template <int T, int W, class Edge = Torus, bool Census = false, bool Fprint = false>
 struct Levels {
   Vec<W> h0[T][3], h1[T][3], cc[T][3];
   Vec<W> acc[T];  // per word: OR of (new ^ old) per produced level L+1
   EdgeState<Edge, W> edge;
   CensusState<Census, T, W> cen;
+  FprintState<Fprint, T, W> fp;
 };
 template <int T, class IO>
-using LevelsOf = Levels<T, IO::W, typename IO::Edge, IO::kCensus>;
+using LevelsOf = Levels<T, IO::W, typename IO::Edge, IO::kCensus, IO::kFprint>;
 
 // Census: the wave counts the level rows [lo, hi) (padded rows) clipped to the
 // tile's owned rows (LifeBlockParams::grid_row_lo / grid_row_hi of a census
@@ -608,6 +650,45 @@ __device__ __forceinline__ void census_init(LevelsOf<T, IO>& st, const LifeBlock
     st.cen.rel = int(in0 - c0);
     st.cen.rows = c1 > c0 ? uint32_t(c1 - c0) : 0u;
   }
+  if constexpr (IO::kFprint) {
+#pragma unroll
+    for (int i = 0; i < IO::W; ++i) {
+      st.fp.fm[i] = lc.fmask[i];
+#pragma unroll
+      for (int L = 0; L < T; ++L) st.fp.acc[L][i] = 0ull;
+    }
+    // Both column modes: the lane's word i is padded word store_col + i.
+    st.fp.gword = lc.store_col - p.own_w0 + p.fp_word0;
+    const int64_t c0 = max(lo, int64_t(p.grid_row_lo)), c1 = min(hi, int64_t(p.grid_row_hi));
+    st.fp.rel = int(in0 - c0);
+    st.fp.rows = c1 > c0 ? uint32_t(c1 - c0) : 0u;
+    st.fp.y0 = p.fp_row0 + int(in0);
+  }
+}
+
+// Fingerprint, end of wave: lane L < T gets the wave's share of generation
+// level L + 1 (every other lane 0): the column keys, then the wave reduction.
+template <int T, class IO>
+__device__ __forceinline__ uint64_t fprint_wave_sums(const LevelsOf<T, IO>& st, int lane) {
+  uint64_t key[IO::W];
+#pragma unroll
+  for (int i = 0; i < IO::W; ++i) key[i] = fingerprint_col_key(uint64_t(int64_t(st.fp.gword + i)));
+  uint64_t mine = 0;
+#pragma unroll
+  for (int L = 0; L < T; ++L) {
+    uint64_t s = 0;
+#pragma unroll
+    for (int i = 0; i < IO::W; ++i) s += st.fp.acc[L][i] * key[i];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += uint64_t(__shfl_xor((unsigned long long)s, d, 64));
+    if (lane == L) mine = s;
+  }
+  return mine;
+}
+
+// The 64-bit slot of the block's first generation in LifeBlockParams::fingerprint.
+__device__ __forceinline__ unsigned long long* fprint_slots(const LifeBlockParams& p) {
+  return p.gen_dev ? p.fingerprint + (*p.gen_dev + p.gen_rel) : p.fingerprint;
 }
 
 // Census, end of wave: lane L < T gets the wave's count of generation level
@@ -647,7 +728,7 @@ __device__ __forceinline__ Vec<W> edge_input(const St& st, Vec<W> cur, int k) {
 // Level L at a step in slot S: push the new level-L row `cur` into the
 // window and produce the level-(L+1) row one row above it.  k: the sweep
 // step (the level-L row is the wave's first input row + k - L), which only the
-// Plane edge policy and the census look at.
+// Plane edge policy, the census and the fingerprint look at.
 template <int T, class IO, int S, int L, int W = IO::W>
 __device__ __forceinline__ Vec<W> level_full(LevelsOf<T, IO>& st, const Vec<W>& cur_in, int k = 0) {
   constexpr int s1 = (S + 1) % 3, s2 = (S + 2) % 3;
@@ -665,6 +746,13 @@ __device__ __forceinline__ Vec<W> level_full(LevelsOf<T, IO>& st, const Vec<W>& 
       // the opaque def as for acc[L] below.
       st.cen.cnt[L][i] += uint32_t(__builtin_popcount(bop3<tt::AND3>(nxt.w[i], st.cen.fm[i], st.cen.row_mask(k, L + 1))));
       asm("" : "+v"(st.cen.cnt[L][i]));
+    }
+    if constexpr (IO::kFprint) {
+      // One mask op and one 64-bit multiply-add (v_mad_u64_u32 with the scalar
+      // row key) per word and level; the opaque def as for acc[L] below.
+      st.fp.acc[L][i] +=
+          uint64_t(bop3<tt::AND3>(nxt.w[i], st.fp.fm[i], st.fp.row_mask(k, L + 1))) * uint64_t(st.fp.row_key(k, L + 1));
+      asm("" : "+v"(st.fp.acc[L][i]));
     }
     st.acc[L].w[i] = bop3<tt::OR_XOR>(st.acc[L].w[i], nxt.w[i], ctr);
     // Opaque def: in straight-line code (prologue / grouped epilogue) hipcc
@@ -856,6 +944,13 @@ void life_block_kernel(const LifeBlockParams p) {
     const uint32_t mine = census_wave_counts<T, IO>(st, lane);
     if (lane < T && mine != 0u)
       __hip_atomic_fetch_add(census_slots(p) + lane, (unsigned long long)mine, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // Fingerprint: likewise, the wave's share modulo 2^64.
+  if constexpr (IO::kFprint) {
+    const uint64_t mine = fprint_wave_sums<T, IO>(st, lane);
+    if (lane < T && mine != 0ull)
+      __hip_atomic_fetch_add(fprint_slots(p) + lane, (unsigned long long)mine, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
   }
 }

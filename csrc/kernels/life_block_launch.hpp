@@ -132,9 +132,9 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
   // a folded wave span its groups' rows in one descriptor (< 2^30 bytes).
   p.fold = 1;
   p.fold_lanes = 64;
-  // Never for a census launch: a folded wave's lanes run the rows of several
-  // groups, and the census row test is wave-uniform.
-  if (p.wrap_w && IO::W == 1 && tune.fold && !IO::kCensus && p.ncolw >= 2 &&
+  // Never for a census or fingerprint launch: a folded wave's lanes run the
+  // rows of several groups, and their row test and row key are wave-uniform.
+  if (p.wrap_w && IO::W == 1 && tune.fold && !kSeries<IO> && p.ncolw >= 2 &&
       (out_rows + 2) * p.pitch < (int64_t(1) << 30)) {
     const int lanes = p.wrap_w - (p.ncolw - 1) * kWaveOut + (IO::XL == kXlaneAdd ? 1 : 2);
     const int f = std::min(4, 64 / lanes);
@@ -149,7 +149,7 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
   // tiles, whose launches alone hold 2 waves per SIMD).  Any other launch
   // first joins the two streams.
   if (ctx.link) {
-    if constexpr (IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus && IO::kBits && IO::W == 1 &&
+    if constexpr (IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && IO::kBits && IO::W == 1 &&
                   (T == 8 || T == 12 || T == 16) &&
                   (IO::XL == kXlaneDpp || IO::XL == kXlaneAdd)) {
       if (tune.group != 0) {
@@ -198,8 +198,9 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
       // strip's last.  Stream launches only (the flags count launches, so a
       // replayed graph would see its own stale flags).
       // Rule kernels (IO::Rule other than Conway) are never linked or chained.
-      // Neither are the plane's kernels (lb::PlaneIO) or the census kernels (lb::CensusIO).
-      if (IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus && ctx.chain) {
+      // Neither are the plane's kernels (lb::PlaneIO), the census kernels
+      // (lb::CensusIO) or the fingerprint kernels (lb::FingerprintIO).
+      if (IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && ctx.chain) {
         LifeBlockParams ch = p;
         ch.fold = 1;
         ch.fold_lanes = 64;
@@ -270,11 +271,11 @@ LaunchResult launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, c
     case 16: return launch_T<16, IO>(p, out_rows, tune, ctx, s);
     case 24:  // byte layout only: fewer byte-grid passes per generation
       // (the adder window never runs T > 16: launch_life_block switches it to DPP)
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus)
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO>)
         return launch_deep<24, IO>(p, out_rows, tune, ctx, s);
       [[fallthrough]];
     case 32:
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus) {
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO>) {
         if (T == 32) return launch_deep<32, IO>(p, out_rows, tune, ctx, s);
       }
       [[fallthrough]];
@@ -345,3 +346,17 @@ namespace rules {
   }
 #define GOL_CENSUS_TU_BITS_DPP GOL_CENSUS_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
 #define GOL_CENSUS_TU_U8_DPP GOL_CENSUS_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))
+
+// Fingerprint kernels (lb::FingerprintIO): as the census kernels;
+// life_block_fprint_<variant>.hip, each one line:
+//   GOL_FPRINT_TU_BITS_DPP | GOL_FPRINT_TU_U8_DPP
+#define GOL_FPRINT_TU(variant, IO_)                                                      \
+  namespace gol {                                                                        \
+  namespace hipk {                                                                       \
+  GOL_LIFE_VARIANT(launch_fprint_##variant) {                                            \
+    return lb::launch_variant<lb::FingerprintIO<IO_>>(p, out_rows, T, tune, ctx, s);     \
+  }                                                                                      \
+  }                                                                                      \
+  }
+#define GOL_FPRINT_TU_BITS_DPP GOL_FPRINT_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
+#define GOL_FPRINT_TU_U8_DPP GOL_FPRINT_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))

@@ -346,8 +346,8 @@ void life_group_kernel(const LifeBlockParams p) {
   // recomputes its upper neighbour's last row, identically), so the wave's
   // control flow is the same for all of them; lanes carry their group's row
   // offset in their read / store offsets.
-  // fold == 1 (launch_T); rule, plane and census kernels are never chained (the wait compiles out)
-  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && !IO::kCensus && p.chain_buf != nullptr;
+  // fold == 1 (launch_T); rule, plane, census and fingerprint kernels are never chained (the wait compiles out)
+  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && p.chain_buf != nullptr;
   int kcol, grp, nsub = 1, sub_lanes = 64;
   if (p.fold > 1 && blk >= (p.ncolw - 1) * p.nseg) {
     kcol = p.ncolw - 1;
@@ -505,6 +505,20 @@ void life_group_kernel(const LifeBlockParams p) {
       for (int j = 0; j < M; ++j) sum += cen[j * 16 + lane];
       if (sum != 0ull)
         __hip_atomic_fetch_add(census_slots(p) + lane, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // Fingerprint: likewise, the group's share modulo 2^64.
+  if constexpr (IO::kFprint) {
+    __shared__ unsigned long long fps[M * 16];
+    const uint64_t mine = fprint_wave_sums<T, IO>(st, lane);
+    if (lane < T) fps[m * 16 + lane] = mine;
+    __syncthreads();
+    if (m == 0 && lane < T) {
+      unsigned long long sum = 0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) sum += fps[j * 16 + lane];
+      if (sum != 0ull)
+        __hip_atomic_fetch_add(fprint_slots(p) + lane, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   if constexpr (IO::kLinked) {  // every wave's rows are written through, then one flag

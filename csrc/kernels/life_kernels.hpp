@@ -147,6 +147,17 @@ struct LifeBlockParams {
   // launch is never a plane launch and passes the tile's owned rows in
   // grid_row_lo / grid_row_hi.  Null in every other launch.
   unsigned long long* census;
+  // Fingerprint (BlockArgs::fingerprint; the kernels of lb::FingerprintIO;
+  // gol/fingerprint.hpp): the 64-bit slot of the block's first generation,
+  // addressed like `census`.  Every wave or group adds its share of each
+  // generation's fingerprint: the owned words of the rows it counts (the
+  // census's rows; grid_row_lo / grid_row_hi hold the tile's owned rows),
+  // weighted by the keys of their global row - padded row r is global row
+  // fp_row0 + r, in 32 bits as for bnd_g (SGPR budget) - and global word:
+  // padded word own_w0 is global word fp_word0.  Null in every other launch.
+  unsigned long long* fingerprint;
+  int fp_row0;
+  int fp_word0;
 };
 
 constexpr int64_t kWgTraceWaves = int64_t(1) << 20;
@@ -354,6 +365,8 @@ std::string life_block_variant(Layout layout, const LifeTuning& tune);
 std::string life_block_plane_variant(Layout layout, const LifeTuning& tune);
 // The same for a census engine (BlockArgs::census).
 std::string life_block_census_variant(Layout layout, const LifeTuning& tune);
+// The same for a fingerprint engine (BlockArgs::fingerprint).
+std::string life_block_fprint_variant(Layout layout, const LifeTuning& tune);
 // Largest T that keeps 2 waves/SIMD for the variant's words-per-lane.
 int life_block_max_T(Layout layout, const LifeTuning& tune);
 
@@ -374,6 +387,10 @@ GOL_LIFE_VARIANT(launch_plane_u8_dpp);
 // columns), but it is a second set of kernels.
 GOL_LIFE_VARIANT(launch_census_bits_dpp);
 GOL_LIFE_VARIANT(launch_census_u8_dpp);
+// The per-generation grid fingerprint (lb::FingerprintIO;
+// life_block_fprint_*.hip): scheduled like the census.
+GOL_LIFE_VARIANT(launch_fprint_bits_dpp);
+GOL_LIFE_VARIANT(launch_fprint_u8_dpp);
 // The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave
 // groups of short segments; life_block_bits_w1_dpp_quiet.hip): wrap-mode
 // blocks over a row ring's owned rows only.  Returns the tiles launched, 0
@@ -465,6 +482,16 @@ void launch_rotate_cols(const uint8_t* src, uint8_t* dst, const TileGeom& g, int
 // (the two geometries hold the same owned tile; halos and pitch may differ).
 void launch_convert_rows(const uint8_t* src, const TileGeom& gs, uint8_t* dst, const TileGeom& gd, int64_t i0,
                          int64_t nrows, hipStream_t s);
+// Adds the fingerprint share (gol/fingerprint.hpp) of the tile's owned cells to
+// *out64: owned row 0 is global row global_row0, the first owned word global
+// word global_word0.  Either layout; the last word's cells beyond W count as 0.
+void launch_fingerprint(const uint8_t* buf, const TileGeom& g, int64_t global_row0, int64_t global_word0,
+                        unsigned long long* out64, hipStream_t s);
+// The owned rows of src (whole pitch) into dst, a tile buffer of the same
+// geometry (src may be a row ring; dst's halo rows are left alone).
+void launch_copy_owned_rows(const uint8_t* src, uint8_t* dst, const TileGeom& g, hipStream_t s);
+// Sets *flag to 1 if any owned cell of two tiles of geometry g differs.
+void launch_equal(const uint8_t* a, const uint8_t* b, const TileGeom& g, uint32_t* flag, hipStream_t s);
 
 }  // namespace hipk
 }  // namespace gol

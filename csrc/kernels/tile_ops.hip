@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gol/backend.hpp"
+#include "gol/fingerprint.hpp"
 #include "life_kernels.hpp"
 
 namespace gol {
@@ -118,6 +119,56 @@ __global__ void alive_k(const uint8_t* buf, int64_t pitch, int64_t row0, int64_t
     if (count) atomicAdd(count, local);
     if (any_flag) *any_flag = 1u;  // idempotent: no atomic needed
   }
+}
+
+// Fingerprint share of the owned cells (gol/fingerprint.hpp): one owned word
+// (32 cells: a uint32, or 32 bytes of 0/1) per thread and step; nw words per
+// row, the last one holding `tail` cells (0: all 32).
+__global__ void fingerprint_k(const uint8_t* buf, int64_t pitch, int64_t row0, int64_t H, int64_t byte0, int64_t nw,
+                              int tail, bool bits, int64_t grow0, int64_t gword0, unsigned long long* out) {
+  const int64_t n = H * nw;
+  unsigned long long local = 0;
+  for (int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; t < n; t += int64_t(gridDim.x) * blockDim.x) {
+    const int64_t i = t / nw, j = t - i * nw;
+    const int cells = (j == nw - 1 && tail) ? tail : 32;
+    uint32_t w = 0;
+    if (bits) {
+      w = *reinterpret_cast<const uint32_t*>(buf + (row0 + i) * pitch + byte0 + 4 * j);
+      if (cells < 32) w &= (1u << cells) - 1u;
+    } else {
+      const uint8_t* p = buf + (row0 + i) * pitch + byte0 + 32 * j;
+      for (int b = 0; b < cells; ++b) w |= uint32_t(p[b] & 1u) << b;
+    }
+    local += uint64_t(w) * uint64_t(fingerprint_row_key(uint32_t(grow0 + i))) * fingerprint_col_key(uint64_t(gword0 + j));
+  }
+  // wave64 reduction, one atomic per wave
+  for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+  if ((threadIdx.x & 63) == 0 && local) atomicAdd(out, local);
+}
+
+// Any owned cell that differs between two tiles of one geometry: the owned
+// span of each row in 4-byte chunks, the last one masked, as alive_k.
+__global__ void equal_k(const uint8_t* a, const uint8_t* b, int64_t pitch, int64_t row0, int64_t H, int64_t byte0,
+                        int64_t nbytes, uint32_t* flag) {
+  const int64_t chunks = ceil_div(nbytes, 4);
+  const int64_t n = H * chunks;
+  uint32_t diff = 0;
+  for (int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; t < n; t += int64_t(gridDim.x) * blockDim.x) {
+    const int64_t i = t / chunks, j = t - i * chunks;
+    const int64_t o = (row0 + i) * pitch + byte0 + 4 * j;
+    uint32_t v = *reinterpret_cast<const uint32_t*>(a + o) ^ *reinterpret_cast<const uint32_t*>(b + o);
+    const int64_t rem = nbytes - 4 * j;
+    if (rem < 4) v &= (1u << (8 * rem)) - 1u;
+    diff |= v;
+  }
+  if (diff) *flag = 1u;  // idempotent: no atomic needed
+}
+
+// The owned rows of a tile, whole pitch, 16 bytes per thread and step (a row
+// pitch is a multiple of 256 bytes).
+__global__ void copy_rows_k(const uint4* src, uint4* dst, int64_t n) {
+  for (int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; t < n; t += int64_t(gridDim.x) * blockDim.x)
+    dst[t] = src[t];
 }
 
 __global__ void load_rows_bits(uint32_t* buf, int64_t pitch_w, int64_t first_row, int hw, int64_t ow,
@@ -345,6 +396,27 @@ void launch_alive(const uint8_t* buf, const TileGeom& g, uint32_t* any_flag,
   const int64_t n = g.H * ceil_div(nbytes, 4);
   hipLaunchKernelGGL(alive_k, dim3(grid_for(n)), dim3(kBlock), 0, s, buf, g.pitch, int64_t(g.row0()),
                      g.H, byte0, nbytes, any_flag, count);
+}
+
+void launch_fingerprint(const uint8_t* buf, const TileGeom& g, int64_t global_row0, int64_t global_word0,
+                        unsigned long long* out64, hipStream_t s) {
+  const int64_t nw = ceil_div(g.W, 32);
+  hipLaunchKernelGGL(fingerprint_k, dim3(grid_for(g.H * nw)), dim3(kBlock), 0, s, buf, g.pitch, int64_t(g.row0()), g.H,
+                     g.offset(0, g.cell0()), nw, int(g.W % 32), g.layout == Layout::Bits, global_row0, global_word0,
+                     out64);
+}
+
+void launch_equal(const uint8_t* a, const uint8_t* b, const TileGeom& g, uint32_t* flag, hipStream_t s) {
+  const int64_t nbytes = g.span_bytes(g.W);
+  hipLaunchKernelGGL(equal_k, dim3(grid_for(g.H * ceil_div(nbytes, 4))), dim3(kBlock), 0, s, a, b, g.pitch,
+                     int64_t(g.row0()), g.H, g.offset(0, g.cell0()), nbytes, flag);
+}
+
+void launch_copy_owned_rows(const uint8_t* src, uint8_t* dst, const TileGeom& g, hipStream_t s) {
+  GOL_REQUIRE(g.pitch % 16 == 0, "copy_owned_rows: pitch must be a multiple of 16 bytes");
+  const int64_t n = g.H * (g.pitch / 16), o = g.row0() * g.pitch;
+  hipLaunchKernelGGL(copy_rows_k, dim3(grid_for(n)), dim3(kBlock), 0, s, reinterpret_cast<const uint4*>(src + o),
+                     reinterpret_cast<uint4*>(dst + o), n);
 }
 
 void launch_load_rows(uint8_t* buf, const TileGeom& g, const uint8_t* stage, int64_t ld, int64_t r0,

@@ -22,10 +22,34 @@
 #include <vector>
 
 #include "gol/backend.hpp"
+#include "gol/fingerprint.hpp"
 #include "gol/parallel.hpp"
 
 namespace gol {
 namespace {
+
+// Fingerprint of one padded row of a tile whose first owned cell is global
+// cell col0 (gol/fingerprint.hpp): sum over the owned words of word * A(j),
+// without the row key.  col0 need not be a multiple of 32: a tile word then
+// straddles two global words, shifted by s = col0 % 32.
+struct FingerprintCols {
+  int64_t w0 = 0, nw = 0;  // first owned padded word, owned words
+  int s = 0;
+  std::vector<uint64_t> key;  // A(col0 / 32 + i), i in [0, nw]
+  FingerprintCols() = default;
+  FingerprintCols(const TileGeom& g, int64_t col0) : w0(g.hw), nw(ceil_div(g.W, 32)), s(int(col0 % 32)) {
+    for (int64_t i = 0; i <= nw; ++i) key.push_back(fingerprint_col_key(uint64_t(col0 / 32 + i)));
+  }
+  uint64_t row(const uint32_t* words, const uint32_t* owned) const {
+    uint64_t f = 0;
+    for (int64_t i = 0; i < nw; ++i) {
+      const uint32_t w = words[w0 + i] & owned[w0 + i];
+      f += uint64_t(uint32_t(w << s)) * key[size_t(i)];
+      if (s) f += uint64_t(w >> (32 - s)) * key[size_t(i + 1)];
+    }
+    return f;
+  }
+};
 
 inline uint32_t pack32(const uint8_t* p) {
   uint32_t w = 0;
@@ -196,6 +220,15 @@ class CpuBackend final : public Backend {
   // The census with any rule, on the torus and the plane (run_block counts
   // the level rows of its bands).
   bool supports_census(Layout, Rule, Boundary) const override { return true; }
+  // The fingerprint likewise, with or without the census, at any tile offset.
+  bool supports_fingerprint(Layout, Rule, Boundary, bool) const override { return true; }
+  void fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
+                   uint64_t* out64) override;
+  void tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) override;
+  void copy_owned_rows(void* dst, const void* src, const TileGeom& g) override {
+    const int64_t o = g.row0() * g.pitch;
+    std::memcpy(static_cast<uint8_t*>(dst) + o, static_cast<const uint8_t*>(src) + o, size_t(g.H * g.pitch));
+  }
   void rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) override;
   void convert_rows(const void* src, const TileGeom& gs, void* dst, const TileGeom& gd, int64_t r0,
                     int64_t n) override;
@@ -329,6 +362,11 @@ int CpuBackend::run_block(const BlockArgs& a) {
   // level rows that are the band's own output rows [lo, hi) and the tile's
   // owned rows - the bands' trapezoids overlap, their output rows do not.
   std::vector<uint64_t> pops(a.census ? size_t(nb * T) : 0, 0);
+  // Fingerprint (BlockArgs::fingerprint): the same rows, each owned word
+  // weighted by the keys of its global row and word (gol/fingerprint.hpp).
+  std::vector<uint64_t> fps(a.fingerprint ? size_t(nb * T) : 0, 0);
+  const FingerprintCols fpc = a.fingerprint ? FingerprintCols(g, a.global_col0) : FingerprintCols();
+  GOL_REQUIRE(!(a.fingerprint && drift), "run_block: the fingerprint needs a frame that does not drift");
   auto* in = static_cast<const uint8_t*>(a.in);
   auto* out = static_cast<uint8_t*>(a.out);
   const int64_t P = Wp + 2;  // row stride of the level buffers: a zero word either side
@@ -390,6 +428,12 @@ int CpuBackend::run_block(const BlockArgs& a) {
               pops[size_t(band * T + L)] += live;
             }
           }
+          if (a.fingerprint) {
+            const int64_t r = lo - T + L + n - 2;
+            if (r >= lo && r < hi && r >= g.Dv && r < g.Dv + g.H)
+              fps[size_t(band * T + L)] +=
+                  fpc.row(dst, owned.data()) * uint64_t(fingerprint_row_key(uint32_t(a.global_row0 + r - g.Dv)));
+          }
           if (!last) {
             hsum_row(dst, Wp, hs0(L + 1, sd), hs1(L + 1, sd));
             ++cnt[size_t(L + 1)];
@@ -421,7 +465,44 @@ int CpuBackend::run_block(const BlockArgs& a) {
     for (int L = 1; L <= T; ++L)
       for (int64_t b = 0; b < nb; ++b) a.census[a.gen_base + L - a.flags_base] += pops[size_t(b * T + L - 1)];
   }
+  if (a.fingerprint) {
+    GOL_REQUIRE(!a.gen_dev && a.gen_base >= a.flags_base, "run_block: fingerprint block before its window");
+    for (int L = 1; L <= T; ++L)
+      for (int64_t b = 0; b < nb; ++b) a.fingerprint[a.gen_base + L - a.flags_base] += fps[size_t(b * T + L - 1)];
+  }
   return drift;
+}
+
+void CpuBackend::fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
+                             uint64_t* out64) {
+  const FingerprintCols fpc(g, global_col0);
+  const int64_t Wp = g.Wp();
+  std::vector<uint32_t> row(static_cast<size_t>(Wp)), owned(static_cast<size_t>(Wp));
+  for (int64_t c = 0; c < Wp; ++c) owned[size_t(c)] = owned_mask(g, c);
+  auto* in = static_cast<const uint8_t*>(buf);
+  uint64_t f = 0;
+  for (int64_t i = 0; i < g.H; ++i) {
+    const int64_t r = g.row0() + i;
+    if (g.layout == Layout::Bits)
+      std::memcpy(row.data(), in + r * g.pitch, size_t(4 * Wp));
+    else
+      for (int64_t c = 0; c < Wp; ++c) row[size_t(c)] = read_word(in, g, r, c);
+    f += fpc.row(row.data(), owned.data()) * uint64_t(fingerprint_row_key(uint32_t(global_row0 + i)));
+  }
+  *out64 += f;
+}
+
+void CpuBackend::tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) {
+  auto* pa = static_cast<const uint8_t*>(a);
+  auto* pb = static_cast<const uint8_t*>(b);
+  const int64_t off = g.offset(0, g.cell0()), n = g.span_bytes(g.W);
+  for (int64_t i = 0; i < g.H; ++i) {
+    const int64_t o = (g.row0() + i) * g.pitch + off;
+    if (std::memcmp(pa + o, pb + o, size_t(n)) != 0) {
+      *flag = 1u;
+      return;
+    }
+  }
 }
 
 void CpuBackend::rotate_cols(const void* src, void* dst, const TileGeom& g, int64_t shift) {

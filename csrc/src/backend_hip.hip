@@ -645,7 +645,8 @@ class HipBackend final : public Backend {
     // link=1 / chain=1 included.
     // Nor are the plane's kernels (BlockArgs::plane), which never skip either.
     // The census kernels (BlockArgs::census) likewise.
-    const bool conway = rule_is_default(a.rule) && !a.plane && !a.census;
+    // And the fingerprint kernels (BlockArgs::fingerprint).
+    const bool conway = rule_is_default(a.rule) && !a.plane && !a.census && !a.fingerprint;
     // Wave trace: launch trace_at_ (its `pair` form: and the next one).
     const int64_t traced = trace_at_ < 0 ? -1 : launches_ - trace_at_;
     const bool trace = traced == 0 || (traced == 1 && trace_pair_);
@@ -801,17 +802,22 @@ class HipBackend final : public Backend {
   // (docs/PERFORMANCE.md "Life-like rules").  Their byte kernels stop at
   // T = 16, and they never link.
   KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule, Boundary boundary,
-                             bool census) const override {
+                             bool census, bool fingerprint) const override {
     // The bounded plane: the DPP window's choice of T (its kernels stop at
     // T = 16 in both layouts), never drifting, never linked, never skipping.
     // The census: the same (its kernels are the DPP window's, T <= 16).
-    if (boundary == Boundary::Dead || census) {
+    // The fingerprint: as the census.
+    if (boundary == Boundary::Dead || census || fingerprint) {
       KernelChoice k = choose_conway(l, rows, cols, tmax_req, hipk::kXlaneDpp);
       k.tmax = std::min(k.tmax, 16);
       // The bit layout's T = 16 census kernel takes 153 VGPRs (3 waves per
       // SIMD) where T = 12 takes 122 (4 waves): 32768^2 15.48 against 14.08 ms
       // per 1000 generations (docs/PERFORMANCE.md "Population census").
       if (census && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
+      // The bit layout's fingerprint kernels take 181 VGPRs at T = 16 (2 waves
+      // per SIMD), 141 at T = 12 (3 waves) and 102 at T = 8 (4 waves): the
+      // census's 12 until measured (docs/PERFORMANCE.md "Cycle detection").
+      if (fingerprint && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
       k.drift = k.link = false;
       return k;
     }
@@ -870,6 +876,26 @@ class HipBackend final : public Backend {
     return "census=1 with u8_kernel=lds: the LDS-tiled byte kernels have no census";
   }
   std::string census_kernel(Layout l) const override { return hipk::life_block_census_variant(l, tune_); }
+  // The fingerprint: what the census runs on, and not together with it.
+  bool supports_fingerprint(Layout l, Rule rule, Boundary b, bool census) const override {
+    return !census && supports_census(l, rule, b);
+  }
+  std::string unsupported_fingerprint(Layout l, Rule rule, Boundary b, bool census) const override {
+    if (b != Boundary::Torus)
+      return std::string("fingerprint=1 with boundary=") + boundary_name(b) +
+             " on the HIP engine: the fingerprint kernels are compiled for the torus only (the cpu and ref engines "
+             "fingerprint the plane)";
+    if (!rule_is_default(rule))
+      return "fingerprint=1 with rule " + rule_string(rule) +
+             " on the HIP engine: the fingerprint kernels are compiled for B3/S23 only (the cpu and ref engines "
+             "fingerprint under any rule)";
+    if (l == Layout::U8 && tune_.u8_lds)
+      return "fingerprint=1 with u8_kernel=lds: the LDS-tiled byte kernels have no fingerprint";
+    (void)census;
+    return "fingerprint=1 with census=1 on the HIP engine: a temporal block runs one fused per-generation series "
+           "(the cpu and ref engines run both)";
+  }
+  std::string fingerprint_kernel(Layout l) const override { return hipk::life_block_fprint_variant(l, tune_); }
   KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req, int xlane) const {
     KernelChoice k{tmax_req > 0 ? tmax_req : preferred_tmax(l), false};
     if (l == Layout::U8 && tmax_req <= 0 && !tune_.u8_lds) {
@@ -1016,6 +1042,28 @@ class HipBackend final : public Backend {
     GOL_ON_DEVICE();
     HIP_CHECK(hipMemsetAsync(flag, 0, 4, stream_));
     hipk::launch_alive(static_cast<const uint8_t*>(buf), g, flag, nullptr, stream_);
+    HIP_CHECK(hipGetLastError());
+  }
+  void fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
+                   uint64_t* out64) override {
+    GOL_REQUIRE(global_col0 % 32 == 0, "fingerprint: tile off the global word grid");
+    const int64_t global_word0 = global_col0 / 32;
+    join_streams();
+    GOL_ON_DEVICE();
+    hipk::launch_fingerprint(static_cast<const uint8_t*>(buf), g, global_row0, global_word0,
+                             reinterpret_cast<unsigned long long*>(out64), stream_);
+    HIP_CHECK(hipGetLastError());
+  }
+  void copy_owned_rows(void* dst, const void* src, const TileGeom& g) override {
+    join_streams();
+    GOL_ON_DEVICE();
+    hipk::launch_copy_owned_rows(static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), g, stream_);
+    HIP_CHECK(hipGetLastError());
+  }
+  void tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) override {
+    join_streams();
+    GOL_ON_DEVICE();
+    hipk::launch_equal(static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(b), g, flag, stream_);
     HIP_CHECK(hipGetLastError());
   }
   int64_t alive_count(const void* buf, const TileGeom& g) override {

@@ -18,6 +18,7 @@
 #include "gol/cpu_ref.hpp"
 #include "gol/decomp.hpp"
 #include "gol/engine.hpp"
+#include "gol/fingerprint.hpp"
 #include "gol/io.hpp"
 #include "gol/numa.hpp"
 #include "gol/transport.hpp"
@@ -178,6 +179,12 @@ PYBIND11_MODULE(_gol, m) {
         return b.supports_census(l, parse_rule(rule), parse_boundary(boundary));
       })
       .def("census_kernel", &Backend::census_kernel)
+      .def("supports_fingerprint",
+           [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary, bool census) {
+             return b.supports_fingerprint(l, parse_rule(rule), parse_boundary(boundary), census);
+           },
+           py::arg("layout"), py::arg("rule"), py::arg("boundary"), py::arg("census") = false)
+      .def("fingerprint_kernel", &Backend::fingerprint_kernel)
       .def("bind_thread", &Backend::bind_thread);
   m.def("cpu_backend",
         [](int threads, int drift, std::optional<Tuning> tune) {
@@ -281,6 +288,7 @@ PYBIND11_MODULE(_gol, m) {
       .def_property("boundary", [](const EngineConfig& c) { return std::string(boundary_name(c.boundary)); },
                     [](EngineConfig& c, const std::string& s) { c.boundary = parse_boundary(s); })
       .def_readwrite("census", &EngineConfig::census)
+      .def_readwrite("fingerprint", &EngineConfig::fingerprint)
       .def_readwrite("decomp", &EngineConfig::decomp)
       .def_readwrite("gen_limit", &EngineConfig::gen_limit)
       .def_readwrite("check_similarity", &EngineConfig::check_similarity)
@@ -321,6 +329,24 @@ PYBIND11_MODULE(_gol, m) {
       .def_property_readonly("population", [](const RunResult& r) {
         py::array_t<int64_t> a(static_cast<py::ssize_t>(r.population.size()));
         std::copy(r.population.begin(), r.population.end(), a.mutable_data());
+        return a;
+      })
+      .def_property_readonly("fingerprint", [](const RunResult& r) {
+        py::array_t<uint64_t> a(static_cast<py::ssize_t>(r.fingerprint.size()));
+        std::copy(r.fingerprint.begin(), r.fingerprint.end(), a.mutable_data());
+        return a;
+      });
+  py::class_<CycleResult>(m, "CycleResult")
+      .def_readonly("period", &CycleResult::period)
+      .def_readonly("generation", &CycleResult::generation)
+      .def_readonly("repeats_from", &CycleResult::repeats_from)
+      .def_readonly("confirmations", &CycleResult::confirmations)
+      .def_readonly("false_candidates", &CycleResult::false_candidates)
+      .def_readonly("stop_reason", &CycleResult::stop_reason)
+      .def_readonly("loop_ms", &CycleResult::loop_ms)
+      .def_property_readonly("fingerprint", [](const CycleResult& r) {
+        py::array_t<uint64_t> a(static_cast<py::ssize_t>(r.fingerprint.size()));
+        std::copy(r.fingerprint.begin(), r.fingerprint.end(), a.mutable_data());
         return a;
       });
 
@@ -406,6 +432,9 @@ PYBIND11_MODULE(_gol, m) {
       .def("init_random", &Engine::init_random, py::arg("seed"), py::arg("density") = 0.5,
            py::call_guard<py::gil_scoped_release>())
       .def("alive_count", &Engine::alive_count, py::call_guard<py::gil_scoped_release>())
+      .def("fingerprint", &Engine::fingerprint, py::call_guard<py::gil_scoped_release>())
+      .def("find_cycle", &Engine::find_cycle, py::arg("max_gens"), py::arg("max_period") = 64, py::arg("chunk") = 0,
+           py::call_guard<py::gil_scoped_release>())
       .def("run", &Engine::run, py::call_guard<py::gil_scoped_release>())
       .def("advance", &Engine::advance, py::call_guard<py::gil_scoped_release>())
       .def("run_until", &Engine::run_until, py::call_guard<py::gil_scoped_release>())
@@ -567,7 +596,7 @@ PYBIND11_MODULE(_gol, m) {
   m.def("cpu_reference_run",
         [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, int64_t gen_limit,
            bool check_similarity, int sim_freq, int threads, const std::string& rule, const std::string& boundary,
-           bool census) -> py::tuple {
+           bool census, bool fingerprint) -> py::tuple {
           GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
           int64_t H = a.shape(0), W = a.shape(1);
           std::vector<uint8_t> g(a.data(), a.data() + W * H);
@@ -576,16 +605,34 @@ PYBIND11_MODULE(_gol, m) {
           RefResult r;
           {
             py::gil_scoped_release rel;
-            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl, bd, census);
+            r = cpu_reference_run(g, W, H, gen_limit, check_similarity, sim_freq, threads, rl, bd, census,
+                                  fingerprint);
           }
-          if (!census) return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W));
-          py::array_t<int64_t> pop(static_cast<py::ssize_t>(r.population.size()));
-          std::copy(r.population.begin(), r.population.end(), pop.mutable_data());
-          return py::make_tuple(r.generations, r.loop_ms, to_array(std::move(g), H, W), pop);
+          // (generations, ms, grid), then the population if asked for, then the fingerprints if asked for.
+          py::list out;
+          out.append(r.generations);
+          out.append(r.loop_ms);
+          out.append(to_array(std::move(g), H, W));
+          if (census) {
+            py::array_t<int64_t> pop(static_cast<py::ssize_t>(r.population.size()));
+            std::copy(r.population.begin(), r.population.end(), pop.mutable_data());
+            out.append(pop);
+          }
+          if (fingerprint) {
+            py::array_t<uint64_t> fp(static_cast<py::ssize_t>(r.fingerprint.size()));
+            std::copy(r.fingerprint.begin(), r.fingerprint.end(), fp.mutable_data());
+            out.append(fp);
+          }
+          return py::tuple(out);
         },
         py::arg("grid"), py::arg("gen_limit") = 1000, py::arg("check_similarity") = true,
         py::arg("sim_freq") = 3, py::arg("threads") = 1, py::arg("rule") = "B3/S23",
-        py::arg("boundary") = "torus", py::arg("census") = false);
+        py::arg("boundary") = "torus", py::arg("census") = false, py::arg("fingerprint") = false);
+  // The grid fingerprint of an H x W array of cells (gol/fingerprint.hpp), on the host.
+  m.def("grid_fingerprint", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a) {
+    GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
+    return grid_fingerprint(a.data(), a.shape(1), a.shape(1), a.shape(0));
+  });
 
   // ---- bitop3 / rule emulation (for kernel-level tests) ----
   m.def("rule_words", [](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2,

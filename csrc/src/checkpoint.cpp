@@ -137,6 +137,7 @@ void checkpoint_commit(const std::string& dir, const std::string& grid_path, Che
   if (parse_boundary(m.boundary) != Boundary::Torus)
     o << "\n \"boundary\": \"" << boundary_name(parse_boundary(m.boundary)) << "\",";
   if (m.census) o << "\n \"census\": true,";
+  if (m.fingerprint) o << "\n \"fingerprint\": true,";
   o << "\n \"grid\": \"" << m.grid << "\"\n}";
   const std::string tmp = dir + "/meta.json.tmp", fin = dir + "/meta.json";
   {
@@ -192,6 +193,9 @@ CheckpointMeta checkpoint_load(const std::string& dir) {
   const std::string census = json_field(js, "census");
   GOL_REQUIRE(census.empty() || census == "true" || census == "false", "checkpoint '" + dir + "': bad census");
   m.census = census == "true";
+  const std::string fprint = json_field(js, "fingerprint");
+  GOL_REQUIRE(fprint.empty() || fprint == "true" || fprint == "false", "checkpoint '" + dir + "': bad fingerprint");
+  m.fingerprint = fprint == "true";
   const std::string grid = json_field(js, "grid");
   if (!grid.empty()) {
     GOL_REQUIRE(checkpoint_grid_name_ok(grid), "checkpoint '" + dir + "': bad grid file name '" + grid +

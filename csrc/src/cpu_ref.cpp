@@ -5,13 +5,14 @@
 #include <memory>
 
 #include "gol/common.hpp"
+#include "gol/fingerprint.hpp"
 #include "gol/parallel.hpp"
 
 namespace gol {
 
 RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, int64_t gen_limit,
                             bool check_similarity, int sim_freq, int threads, Rule rule, Boundary boundary,
-                            bool census) {
+                            bool census, bool fingerprint) {
   GOL_REQUIRE(int64_t(grid.size()) == W * H, "grid size mismatch");
   require_no_b0(rule, rule_string(rule));
   GOL_REQUIRE(sim_freq > 0, "similarity frequency must be positive");
@@ -41,6 +42,7 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
   int64_t generation = 1;
   int counter = 0;
   std::vector<int64_t> population;
+  std::vector<uint64_t> fprints;
   auto t0 = std::chrono::steady_clock::now();
   while (!empty() && generation <= gen_limit) {
     const uint8_t* u = univ;
@@ -81,12 +83,14 @@ RefResult cpu_reference_run(std::vector<uint8_t>& grid, int64_t W, int64_t H, in
       for (int64_t i = 0; i < W * H; ++i) live += univ[i];
       population.push_back(live);
     }
+    if (fingerprint) fprints.push_back(grid_fingerprint(univ, W, W, H));
     ++generation;
   }
   auto t1 = std::chrono::steady_clock::now();
   RefResult r;
   r.generations = generation - 1;
   r.population = std::move(population);
+  r.fingerprint = std::move(fprints);
   r.loop_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
   std::copy(univ, univ + W * H, grid.begin());
   return r;

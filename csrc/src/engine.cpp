@@ -55,6 +55,13 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
                 "of the census's sum over ranks");
     GOL_REQUIRE(cfg_.graphs <= 0, "census=1 with graphs=1: captured epochs are not built for the census");
   }
+  if (cfg_.fingerprint) {
+    // As for the census.
+    GOL_REQUIRE(!cfg_.self_exchange,
+                "fingerprint=1 with self_exchange (--rehearse-rccl): the rehearsal's one-rank communicator is not "
+                "part of the fingerprint's sum over ranks");
+    GOL_REQUIRE(cfg_.graphs <= 0, "fingerprint=1 with graphs=1: captured epochs are not built for the fingerprint");
+  }
   if (cfg_.overlap == 1) cfg_.overlap = 3;  // "on" is the trigger schedule
   int64_t unit = (cfg_.layout == Layout::Bits || cfg_.W % 32 == 0) ? 32 : 1;
   if (cfg_.layout == Layout::Bits)
@@ -77,12 +84,26 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   if (!be_->supports_rule(cl, cfg_.rule)) fail(be_->unsupported_rule(cl, cfg_.rule));
   if (cfg_.census && !be_->supports_census(cl, cfg_.rule, cfg_.boundary))
     fail(be_->unsupported_census(cl, cfg_.rule, cfg_.boundary));
+  if (cfg_.fingerprint) {
+    if (!be_->supports_fingerprint(cl, cfg_.rule, cfg_.boundary, cfg_.census))
+      fail(be_->unsupported_fingerprint(cl, cfg_.rule, cfg_.boundary, cfg_.census));
+    // The device kernels weigh whole 32-cell words: every tile must start on
+    // the global word grid (the same answer on every rank).
+    if (be_->is_device())
+      for (int r = 0; r < dec_.nranks(); ++r)
+        GOL_REQUIRE(dec_.cols(r).begin % 32 == 0,
+                    "fingerprint=1 with decomposition " + dec_.describe() + " of a byte-layout grid " +
+                        std::to_string(cfg_.W) + " cells wide: a tile starts at column " +
+                        std::to_string(dec_.cols(r).begin) +
+                        ", no multiple of 32, so its words do not line up with the fingerprint's word grid (use a "
+                        "decomposition with Px = 1, a width that is a multiple of 32, or the cpu engine)");
+  }
   // Every rank must take the same decision (a drifting frame or a schedule
   // that moves a halo exchange is only consistent in lockstep), so it is
   // made for the smallest tile of the decomposition, not this rank's.
   const Backend::KernelChoice kc =
       be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule,
-                         cfg_.boundary, cfg_.census);
+                         cfg_.boundary, cfg_.census, cfg_.fingerprint);
   tmax_ = std::min(kc.tmax, cl == Layout::U8 && !plane_ ? 32 : 16);
   // Epoch depth: a deeper halo means fewer latency-bound exchanges (or local
   // periodic fills: two ~5 us launches each) but ~D redundant rows per epoch.
@@ -173,7 +194,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // Linked launches (Backend::KernelChoice::link): consecutive blocks of an
   // epoch overlap; anything else on the stream (fills, exchanges, polls)
   // joins the streams first.  Not with column fills between blocks.
-  link_ = kc.link && !cols_filled_ && !plane_ && !cfg_.census;
+  link_ = kc.link && !cols_filled_ && !plane_ && !(cfg_.census || cfg_.fingerprint);
   // Several ranks: every poll is a flag all-reduce on the compute stream
   // (latency-bound), so poll half as often; a stop is still exact and at most
   // two windows late.
@@ -205,11 +226,11 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // words too: the trigger runs on the bit image.
   // Not on the plane (the trigger rides on linked launches).
   // Nor with the census (no linked launches).
-  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger() && !plane_ && !cfg_.census;
+  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger() && !plane_ && !(cfg_.census || cfg_.fingerprint);
   trigger_ = trigger_ok && cfg_.overlap == 3;
   watchdog_s_ = cfg_.watchdog_s > 0 ? cfg_.watchdog_s : cfg_.tune.f("watchdog_s") > 0 ? cfg_.tune.f("watchdog_s") : 900.0;
   use_graphs_ = cfg_.graphs != 0 && be_->supports_graphs() && tr_->capturable() &&
-                (cfg_.graphs > 0 || tr_->size() == 1) && !plane_ && !cfg_.census;
+                (cfg_.graphs > 0 || tr_->size() == 1) && !plane_ && !(cfg_.census || cfg_.fingerprint);
   if (use_graphs_) gen_dev_ = Owned<int64_t>(be_, be_->alloc(sizeof(int64_t)));
   if (use_graphs_) trigger_ = false;  // captured epochs stay on one stream
   // Overlap auto: measure both schedules on the real ranks (see auto_choose);
@@ -251,7 +272,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // a torus that is the same from block to block).  Everything else keeps
   // today's path.
   const Backend::QuietTuning qt = be_->quiet_mode();
-  if (qt.mode != 0 && !plane_ && !cfg_.census && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
+  if (qt.mode != 0 && !plane_ && !(cfg_.census || cfg_.fingerprint) && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
       tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_ && tmax_ == be_->quiet_block() && D_ == tmax_) {
     quiet_.mode = qt.mode;
     quiet_.scout = qt.scout;
@@ -261,7 +282,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Lazy tail (run_impl): single-rank ring tiles whose epochs are one block.
   tail_mode_ = cfg_.tune.i("lazy_tail");
-  tail_ok_ = tail_mode_ != 0 && !plane_ && !cfg_.census && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
+  tail_ok_ = tail_mode_ != 0 && !plane_ && !(cfg_.census || cfg_.fingerprint) && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
   if (tail_ok_) carry_ = Owned<uint32_t>(be_, be_->alloc(size_t(tmax_) * 4));
   gen_ = cfg_.start_gen;
 }
@@ -347,6 +368,123 @@ int64_t Engine::alive_count() {
   be_->synchronize();
   const Tile s = state_tile();
   return be_->alive_count(s.cur(), s.g);
+}
+
+uint64_t Engine::fingerprint() {
+  settle_pending(false);
+  replay_tail();
+  if (drift_ != 0) normalize();  // the fingerprint weighs every cell by its column
+  const Tile s = state_tile();
+  if (!fp_dev_) fp_dev_ = Owned<uint64_t>(be_, be_->alloc(8));
+  be_->join_streams();
+  be_->memset_async(fp_dev_, 0, 8);
+  be_->fingerprint(s.cur(), s.g, rows().begin, cols().begin, fp_dev_);
+  if (tr_->size() > 1) tr_->allreduce_sum_u64(fp_dev_, 1, be_->stream());
+  be_->synchronize();
+  uint64_t f = 0;
+  be_->copy_d2h(&f, fp_dev_, 8);
+  return f;
+}
+
+// Whether the state tile differs from find_cycle's copy in any owned cell, on
+// any rank.
+bool Engine::differs_from_snapshot() {
+  const Tile s = state_tile();
+  be_->join_streams();
+  be_->memset_async(alive_dev_, 0, 4);
+  be_->tiles_differ(s.cur(), snap_.get(), s.g, alive_dev_);
+  if (tr_->size() > 1) tr_->allreduce_max_u32(alive_dev_, 1, be_->stream());
+  be_->synchronize();
+  uint32_t differ = 0;
+  be_->copy_d2h(&differ, alive_dev_, 4);
+  return differ != 0;
+}
+
+CycleResult Engine::find_cycle(int64_t max_gens, int max_period, int64_t chunk) {
+  GOL_REQUIRE(cfg_.fingerprint, "find_cycle needs fingerprint=1 (EngineConfig::fingerprint)");
+  GOL_REQUIRE(max_period >= 1, "find_cycle: max_period must be at least 1");
+  GOL_REQUIRE(chunk >= 0, "find_cycle: chunk must be >= 0");
+  if (chunk == 0) chunk = 256;
+  const int bits = cfg_.tune.i("cycle_match_bits");
+  GOL_REQUIRE(bits >= 0 && bits <= 64, "cycle_match_bits must be 0..64");
+  const uint64_t mask = bits >= 64 ? ~uint64_t(0) : (uint64_t(1) << bits) - 1;
+  const auto t0 = std::chrono::steady_clock::now();
+  CycleResult res;
+  const int64_t g0 = gen_;
+  // F[i]: the fingerprint of generation g0 + i.  Every rank holds the same
+  // series, so every decision below is the same on every rank.
+  std::vector<uint64_t> F{fingerprint()};
+  const auto advance_to = [&](int64_t g, bool stop_early) {
+    RunResult r = run_impl(g, stop_early);
+    F.insert(F.end(), r.fingerprint.begin(), r.fingerprint.end());
+    GOL_REQUIRE(int64_t(F.size()) == gen_ - g0 + 1, "find_cycle: the fingerprint series has a gap");
+    return r;
+  };
+  const auto finish = [&](int64_t period, const char* why) {
+    res.period = period;
+    res.generation = gen_;
+    res.stop_reason = why;
+    // Backwards from the end of the series, on all 64 bits.
+    int64_t e = int64_t(F.size()) - 1 - period;
+    while (e > 0 && F[size_t(e - 1)] == F[size_t(e - 1 + period)]) --e;
+    res.repeats_from = g0 + std::max<int64_t>(e, 0);
+    res.fingerprint.assign(F.begin() + 1, F.end());
+    res.loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return res;
+  };
+  int64_t floor = 0;  // index of the first generation that counts: the last failed confirmation's end
+  while (gen_ < max_gens) {
+    const RunResult r = advance_to(std::min(gen_ + chunk, max_gens), /*stop_early=*/true);
+    // The change flags found grid(g) == grid(g - 1): exact, no confirmation.
+    if (r.first_unchanged >= 0) return finish(1, r.extinct ? "extinction" : "cycle");
+    const int64_t n = int64_t(F.size()) - 1;
+    // A period needs p generations of history behind its p comparisons - except
+    // with cycle_match_bits = 0, where a match is no evidence to wait for:
+    // every period is a candidate at every search (tests: the rejection path).
+    std::vector<int64_t> cand;
+    for (int64_t p = 1; p <= max_period && (mask == 0 || n - 2 * p + 1 >= floor); ++p) {
+      if (mask == 0) {
+        cand.push_back(p);
+        continue;
+      }
+      bool all = true;
+      for (int64_t g = n; g > n - p && all; --g) all = ((F[size_t(g)] ^ F[size_t(g - p)]) & mask) == 0;
+      if (all) cand.push_back(p);
+    }
+    if (cand.empty()) continue;
+    // The candidates and their divisors, ascending: the minimal period
+    // divides every period, so the first that compares equal is minimal.
+    std::vector<int64_t> D;
+    for (int64_t d = 1; d <= cand.back(); ++d)
+      for (int64_t p : cand)
+        if (p % d == 0) {
+          D.push_back(d);
+          break;
+        }
+    const int64_t G = gen_;
+    if (G + D.back() > max_gens) continue;  // the limit comes first
+    const Tile s = state_tile();
+    const size_t bytes = size_t(s.g.bytes());
+    if (!snap_ || snap_bytes_ < bytes) {
+      snap_.reset();
+      snap_ = Owned<>(be_, be_->alloc(bytes));
+      snap_bytes_ = bytes;
+    }
+    be_->copy_owned_rows(snap_.get(), s.cur(), s.g);
+    for (int64_t d : D) {
+      advance_to(G + d, /*stop_early=*/false);
+      if (!differs_from_snapshot()) {
+        ++res.confirmations;
+        return finish(d, "cycle");
+      }
+    }
+    res.false_candidates += int64_t(cand.size());
+    floor = int64_t(F.size()) - 1;
+  }
+  res.generation = gen_;
+  res.fingerprint.assign(F.begin() + 1, F.end());
+  res.loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return res;
 }
 
 int Engine::pick_T(int64_t remaining) const {
@@ -661,6 +799,14 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
                 "census: a temporal block outside the run's window");
     a.census = census_.get();
   }
+  if (fprint_run_) {
+    // As for the census.
+    GOL_REQUIRE(!no_flags_ && !capturing_ && gen_base >= flags_base_ && gen_base + T < flags_base_ + flags_len_,
+                "fingerprint: a temporal block outside the run's window");
+    a.fingerprint = fprint_.get();
+    a.global_row0 = rows().begin;
+    a.global_col0 = cols().begin;
+  }
   a.allow_drift = drift_ok_;
   a.full_width = dec_.Px == 1 && cfg_.W % 32 == 0 && !plane_;
   a.wrap_rows = rows_wrapped_;
@@ -881,7 +1027,9 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
       census_.reset();
       census_ = Owned<uint64_t>(be_, be_->alloc(size_t(flags_len_) * 8));
     }
+    fprint_.reset();  // below: its length is the flags'
   }
+  if (cfg_.fingerprint && !fprint_) fprint_ = Owned<uint64_t>(be_, be_->alloc(size_t(flags_len_) * 8));
   flags_base_ = start;
   be_->memset_async(flags_, 0, size_t(flags_len_) * 4);
   if (cfg_.census) {
@@ -893,6 +1041,12 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
     bool& on;
     ~CensusRunEnd() { on = false; }
   } census_run_end{census_run_};
+  if (cfg_.fingerprint) {
+    GOL_REQUIRE(ahead_ == 0 && drift_ == 0, "fingerprint: a lazy tail or a drifted frame is pending");
+    be_->memset_async(fprint_, 0, size_t(flags_len_) * 8);
+  }
+  fprint_run_ = cfg_.fingerprint;
+  CensusRunEnd fprint_run_end{fprint_run_};
   if (carried > 0)
     be_->copy_2d_async(flags_ + flag_offset(start), carried * 4, carry_.get(), carried * 4, carried * 4, 1);
   if (use_graphs_) {
@@ -993,6 +1147,7 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   }
   if (have_pending) poll_check(pending, &found);
   census_run_ = false;
+  fprint_run_ = false;
   if (via_bits_) bits_live_ = true;  // unpacked when the byte tile is next read (sync_bytes)
   // A poll issued just before an early stop may still run on the side stream
   // (the final alive reduction below uses the same communicator, and the
@@ -1032,6 +1187,17 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
       be_->copy_d2h(counts.data(), dev, size_t(n) * 8);
     }
     res.population.assign(counts.begin(), counts.end());
+  }
+  if (cfg_.fingerprint) {
+    // Likewise; the ranks' shares add up modulo 2^64.
+    const int64_t n = gen_ - start;
+    res.fingerprint.resize(static_cast<size_t>(n));
+    if (n > 0) {
+      uint64_t* dev = fprint_ + flag_offset(start);
+      if (tr_->size() > 1) tr_->allreduce_sum_u64(dev, size_t(n), be_->stream());
+      be_->synchronize();
+      be_->copy_d2h(res.fingerprint.data(), dev, size_t(n) * 8);
+    }
   }
   if (found >= 0) {
     res.first_unchanged = found;

@@ -108,6 +108,9 @@ const std::vector<TuningKey>& tuning_keys() {
       {"overlap_auto", "GOL_OVERLAP_AUTO", "", 's', "fault", "plain | trigger: force the overlap trial's outcome"},
       {"fault_alloc", "GOL_FAULT_ALLOC", "0", 'i', "fault",
        "CPU backend: its N-th allocation fails (what a failed engine construction leaves behind)"},
+      {"cycle_match_bits", "GOL_CYCLE_MATCH_BITS", "64", 'i', "fault",
+       "Engine::find_cycle compares only the low N bits of each fingerprint (0: every period is a candidate at "
+       "every search, which drives the confirmation and rejection path)"},
       // --- CPU emulation of device features ----------------------------------
       {"cpu_ring", "GOL_CPU_RING", "0", 's', "emul", "CPU backend row rings: 0, 1, or fail (mapping fails)"},
       {"cpu_drift", "GOL_CPU_DRIFT", "0", 'i', "emul", "CPU backend's drifting frame (as the adder window)"},

@@ -33,6 +33,13 @@ using namespace gol;
 
 namespace {
 
+// A fingerprint as 16 hex digits.
+std::string hex16(uint64_t v) {
+  char b[24];
+  std::snprintf(b, sizeof b, "%016llx", (unsigned long long)v);
+  return b;
+}
+
 // A JSON string literal of s (quotes, backslashes and control bytes escaped):
 // tuning values such as trace paths are arbitrary text.
 std::string jstr(const std::string& s) {
@@ -63,6 +70,9 @@ struct Options {
   bool boundary_set = false;
   std::string census;  // --census PATH ("": off)
   bool census_on = false;  // --census, or a resumed checkpoint's setting
+  std::string fprint;  // --fingerprint PATH ("": off)
+  bool fprint_on = false;  // --fingerprint, --cycle, or a resumed checkpoint's setting
+  int cycle = 0;  // --cycle P (0: off)
   std::string decomp = "auto";
   std::string comm = "auto";  // auto | thread | rccl (in-process ranks)
   std::string output;  // default: the matching reference build's file (see default_output)
@@ -104,6 +114,12 @@ struct Options {
                "  --census PATH               count the live cells of every generation inside the temporal\n"
                "                              blocks and write 'generation,population' lines to PATH (hip\n"
                "                              engine: B3/S23 on the torus; no lds kernels, graphs)\n"
+               "  --fingerprint PATH          accumulate a position-dependent 64-bit fingerprint of every\n"
+               "                              generation inside the temporal blocks and write\n"
+               "                              'generation,fingerprint' lines (16 hex digits) to PATH (hip\n"
+               "                              engine: B3/S23 on the torus; no lds kernels, graphs, census)\n"
+               "  --cycle P                   run until the grid repeats with a period <= P (confirmed on the\n"
+               "                              cells) or to the generation limit, and print a 'Cycle:' line\n"
                "  --gens N                    GEN_LIMIT (default 1000)\n"
                "  --sim-freq F                SIMILARITY_FREQUENCY (default 3)\n"
                "  --no-similarity             disable the similarity check\n"
@@ -158,6 +174,12 @@ Options parse(int argc, char** argv) {
     else if (a == "--rule") o.rule = parse_rule(next()), o.rule_set = true;
     else if (a == "--boundary") o.boundary = parse_boundary(next()), o.boundary_set = true;
     else if (a == "--census") o.census = next(), o.census_on = true;
+    else if (a == "--fingerprint") o.fprint = next(), o.fprint_on = true;
+    else if (a == "--cycle") {
+      o.cycle = std::atoi(next().c_str());
+      if (o.cycle < 1) throw Error("--cycle: the largest period must be at least 1");
+      o.fprint_on = true;
+    }
     else if (a == "--decomp") o.decomp = next();
     else if (a == "--comm") o.comm = next();
     else if (a == "--gens") o.gens = std::atoll(next().c_str()), o.gens_set = true;
@@ -229,6 +251,7 @@ Options parse(int argc, char** argv) {
     o.boundary = ck_boundary;
     // A census is per run: --census counts the resumed run whether or not the first one did.
     o.census_on = o.census_on || m.census;
+    o.fprint_on = o.fprint_on || m.fingerprint;
     o.W = m.W;
     o.H = m.H;
     o.input = checkpoint_grid_path(o.resume);
@@ -293,6 +316,9 @@ int run(const Options& o) {
 
   if (engine == "ref" && (!o.resume.empty() || o.checkpoint_every > 0))
     throw Error("--engine ref is the plain serial loop from generation 0: no checkpoint / resume");
+  if (o.cycle > 0 && (engine == "ref" || o.checkpoint_every > 0))
+    throw Error("--cycle runs Engine::find_cycle: not with --engine ref (the plain serial loop) or --checkpoint-every");
+  CycleResult cyc;
   if (engine == "ref") {
     // Exact serial semantics (src/game.c), every generation evaluated eagerly.
     auto t0 = std::chrono::steady_clock::now();
@@ -307,8 +333,9 @@ int run(const Options& o) {
     }
     read_ms = ms_since(t0);
     RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule,
-                                     o.boundary, o.census_on);
+                                     o.boundary, o.census_on, o.fprint_on);
     res.population = rr.population;
+    res.fingerprint = rr.fingerprint;
     res.generations = rr.generations;
     res.loop_ms = rr.loop_ms;
     res.executed = rr.generations;
@@ -327,6 +354,7 @@ int run(const Options& o) {
     cfg.rule = o.rule;
     cfg.boundary = o.boundary;
     cfg.census = o.census_on;
+    cfg.fingerprint = o.fprint_on;
     cfg.decomp = o.decomp;
     cfg.gen_limit = o.gens;
     cfg.check_similarity = o.similarity;
@@ -432,7 +460,21 @@ int run(const Options& o) {
     RunResult total;
     const int64_t limit = o.gens;
     int64_t checkpoints_written = 0;
-    for (;;) {
+    if (o.cycle > 0) {
+      // --cycle: Engine::find_cycle instead of the run loop; every rank takes
+      // the same decisions and returns the same result.
+      const int64_t gen0 = engines[0]->generation();
+      std::vector<CycleResult> cycles(P);
+      par([&](int r) { cycles[r] = engines[r]->find_cycle(limit, o.cycle); });
+      cyc = cycles[0];
+      for (auto& c : cycles) total.loop_ms = std::max(total.loop_ms, c.loop_ms);
+      total.executed = cyc.generation - gen0;
+      total.generations = cyc.generation;
+      total.stop_reason = cyc.stop_reason;
+      total.extinct = cyc.stop_reason == "extinction";
+      total.fingerprint = cyc.fingerprint;
+    }
+    for (; o.cycle == 0;) {
       const int64_t gen = engines[0]->generation();
       const int64_t target = o.checkpoint_every > 0 ? std::min(limit, gen + o.checkpoint_every) : limit;
       par([&](int r) { results[r] = engines[r]->run_until(target); });
@@ -445,6 +487,7 @@ int run(const Options& o) {
       total.kernel_launches += results[0].kernel_launches;
       // The chunks' series concatenate to the whole run's (every rank holds the global sum).
       total.population.insert(total.population.end(), results[0].population.begin(), results[0].population.end());
+      total.fingerprint.insert(total.fingerprint.end(), results[0].fingerprint.begin(), results[0].fingerprint.end());
       // Per-phase device times: the slowest rank's, like loop_ms.
       for (auto& rr : results) {
         total.phase_timed = total.phase_timed || rr.phase_timed;
@@ -486,6 +529,7 @@ int run(const Options& o) {
         m.rule = rule_string(o.rule);
         m.boundary = boundary_name(o.boundary);
         m.census = o.census_on;
+        m.fingerprint = o.fprint_on;
         // Fault injection (tests): die after the N-th checkpoint's tiles are
         // written, before it is committed.
         if (const int c = o.tune.i("fault_checkpoint_crash"))
@@ -552,8 +596,25 @@ int run(const Options& o) {
         for (size_t i = 0; i < res.population.size(); ++i) f << (i ? ", " : "") << res.population[i];
         f << "]";
       }
+      if (o.fprint_on) {
+        f << ", \"fingerprint\": true, \"fingerprints\": [";
+        for (size_t i = 0; i < res.fingerprint.size(); ++i) f << (i ? ", " : "") << jstr(hex16(res.fingerprint[i]));
+        f << "]";
+      }
+      if (o.cycle > 0)
+        f << ", \"cycle\": {\"period\": " << cyc.period << ", \"generation\": " << cyc.generation
+          << ", \"repeats_from\": " << cyc.repeats_from << ", \"confirmations\": " << cyc.confirmations
+          << ", \"false_candidates\": " << cyc.false_candidates << ", \"stop_reason\": " << jstr(cyc.stop_reason)
+          << ", \"max_period\": " << o.cycle << "}";
       f << "}\n";
     }
+  }
+  // --fingerprint PATH: generation,fingerprint lines (16 hex digits), one per generation of the run.
+  if (!o.fprint.empty()) {
+    std::ofstream f(o.fprint);
+    GOL_REQUIRE(f.good(), "--fingerprint: cannot write '" + o.fprint + "'");
+    for (size_t i = 0; i < res.fingerprint.size(); ++i)
+      f << o.start_gen + 1 + int64_t(i) << "," << hex16(res.fingerprint[i]) << "\n";
   }
   // --census PATH: generation,population lines, one per generation of the run.
   if (!o.census.empty()) {
@@ -580,6 +641,15 @@ int run(const Options& o) {
     std::printf("Generations:\t%d\n", int(res.generations));
     std::printf("Execution time:\t%.2f msecs\n", res.loop_ms);
     std::printf("Finished\n");
+  }
+  // --cycle: one extra line after the usual output.  Period and generation are
+  // confirmed on the cells; "repeat from" is fingerprint evidence.
+  if (o.cycle > 0) {
+    if (cyc.period > 0)
+      std::printf("Cycle: period %lld at generation %lld (fingerprints repeat from %lld)\n", (long long)cyc.period,
+                  (long long)cyc.generation, (long long)cyc.repeats_from);
+    else
+      std::printf("Cycle: none within %lld generations\n", (long long)o.gens);
   }
   std::fflush(stdout);
   if (o.show && !final_grid.empty()) show(final_grid, o.W, o.H);

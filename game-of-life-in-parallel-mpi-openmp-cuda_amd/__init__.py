@@ -10,7 +10,8 @@ per GPU.
 Import as ``gol_amd`` (symlink to this directory).
 """
 from ._native import hip_available, native
-from .models.life import LifeConfig, RunReport, Simulation, make_backend, parse_rule, reference_run, simulate
+from .models.life import (CycleReport, LifeConfig, RunReport, Simulation, grid_fingerprint, make_backend, parse_rule,
+                          reference_run, simulate)
 from .ops.life_ops import life_step, life_step_numpy, life_step_torch, random_grid
 
 __version__ = "0.1.0"
@@ -26,6 +27,6 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["LifeConfig", "RunReport", "Simulation", "make_backend", "reference_run", "simulate",
+__all__ = ["CycleReport", "grid_fingerprint", "LifeConfig", "RunReport", "Simulation", "make_backend", "reference_run", "simulate",
            "life_step", "life_step_numpy", "life_step_torch", "random_grid", "native",
            "hip_available", "parse_rule", "RULES", "__version__"]

@@ -40,6 +40,14 @@ def parse_args(argv=None):
                    help="count the live cells of every generation inside the temporal blocks and write "
                         "'generation,population' lines to PATH, one per generation (hip engine: B3/S23 on the torus, "
                         "no lds kernels, no graphs)")
+    p.add_argument("--fingerprint", default=None, metavar="PATH",
+                   help="accumulate a position-dependent 64-bit fingerprint of every generation inside the temporal "
+                        "blocks and write 'generation,fingerprint' lines (16 hex digits) to PATH (hip engine: B3/S23 "
+                        "on the torus, no lds kernels, no graphs, no census)")
+    p.add_argument("--cycle", type=int, default=None, metavar="P",
+                   help="run until the grid repeats with a period <= P (confirmed on the cells) or to the generation "
+                        "limit, and print one more line: 'Cycle: period p at generation G (fingerprints repeat from "
+                        "E)' or 'Cycle: none within N generations'")
     p.add_argument("--gens", type=int, default=1000, help="GEN_LIMIT")
     p.add_argument("--sim-freq", type=int, default=None, help="SIMILARITY_FREQUENCY (default 3)")
     p.add_argument("--no-similarity", action="store_true")
@@ -92,6 +100,20 @@ def write_census(path: str, g0: int, population) -> None:
             f.write(f"{g0 + 1 + i},{int(v)}\n")
 
 
+def write_fingerprint(path: str, g0: int, fingerprint) -> None:
+    """``generation,fingerprint`` lines (16 hex digits), one per generation after ``g0``."""
+    with open(path, "w") as f:
+        for i, v in enumerate(fingerprint):
+            f.write(f"{g0 + 1 + i},{int(v):016x}\n")
+
+
+def cycle_line(cyc, limit: int) -> str:
+    if cyc.period > 0:
+        return (f"Cycle: period {cyc.period} at generation {cyc.generation} "
+                f"(fingerprints repeat from {cyc.repeats_from})\n")
+    return f"Cycle: none within {limit} generations\n"
+
+
 def print_tuning_keys() -> None:
     from ._native import native  # noqa: PLC0415
 
@@ -117,6 +139,11 @@ def main(argv=None) -> int:
         s, _, d = a.random.partition(":")
         seed, density = int(s), float(d) if d else 0.5
 
+    if a.cycle is not None and a.cycle < 1:
+        raise SystemExit("--cycle: the largest period must be at least 1")
+    if a.cycle is not None and (a.engine == "ref" or a.checkpoint_every > 0):
+        raise SystemExit("--cycle runs Simulation.find_cycle: not with --engine ref (the plain serial loop) or "
+                         "--checkpoint-every")
     if a.engine == "ref":
         import numpy as np  # noqa: PLC0415
 
@@ -128,9 +155,11 @@ def main(argv=None) -> int:
         read_ms = (time.perf_counter() - t0) * 1e3
         out, gens, ms, *pop = reference_run(np.asarray(grid), a.gens, not a.no_similarity, a.sim_freq,
                                             max(1, a.threads), rule=rule, boundary=boundary,
-                                            census=a.census is not None)
+                                            census=a.census is not None, fingerprint=a.fingerprint is not None)
         if a.census is not None:
             write_census(a.census, 0, pop[0])
+        if a.fingerprint is not None:
+            write_fingerprint(a.fingerprint, 0, pop[-1])
         t1 = time.perf_counter()
         if a.output != "none":
             write_grid(a.output, out)
@@ -162,7 +191,8 @@ def main(argv=None) -> int:
                      sim_freq=a.sim_freq, layout=a.layout, decomp=a.decomp, tmax=a.tmax,
                      epoch=a.epoch, poll_gens=a.poll, overlap=a.overlap, graphs=a.graphs,
                      u8_compute=a.u8_compute, tune=tune, rule=rule, boundary=boundary,
-                     census=a.census is not None)
+                     census=a.census is not None,
+                     fingerprint=a.fingerprint is not None or a.cycle is not None)
     src = a.input_file
     if a.resume:
         from .utils.checkpoint import load_checkpoint  # noqa: PLC0415
@@ -178,6 +208,7 @@ def main(argv=None) -> int:
                              f"--sim-freq {a.sim_freq} would shift the similarity checks")
         # A census is per run: --census counts the resumed run whether or not the first one did.
         cfg.census = cfg.census or a.census is not None
+        cfg.fingerprint = cfg.fingerprint or a.fingerprint is not None or a.cycle is not None
         src = str(grid_path)
     sim = Simulation(cfg, transport=transport, backend=backend)
     # Opt-in only: the event pairs would sit inside the loop that loop_ms and
@@ -196,6 +227,13 @@ def main(argv=None) -> int:
         from .utils.checkpoint import run_with_checkpoints  # noqa: PLC0415
 
         rep = run_with_checkpoints(sim, a.checkpoint_every, a.checkpoint_dir, rank == 0, transport.barrier)
+    elif a.cycle is not None:
+        from .models.life import RunReport  # noqa: PLC0415
+
+        cyc = sim.find_cycle(a.gens, a.cycle)
+        rep = RunReport(generations=cyc.generation, executed=cyc.generation - g0, stop_reason=cyc.stop_reason,
+                        loop_ms=cyc.loop_ms, extinct=cyc.stop_reason == "extinction", cells=a.width * a.height,
+                        fingerprint=cyc.fingerprint)
     else:
         rep = sim.run()
 
@@ -223,6 +261,14 @@ def main(argv=None) -> int:
             rec["population"] = [int(v) for v in rep.population]
         if a.census is not None:
             write_census(a.census, g0, rep.population)
+        if cfg.fingerprint:
+            rec["fingerprints"] = [f"{int(v):016x}" for v in rep.fingerprint]
+        if a.fingerprint is not None:
+            write_fingerprint(a.fingerprint, g0, rep.fingerprint)
+        if a.cycle is not None:
+            rec["cycle"] = cyc.as_dict() | {"max_period": a.cycle}
+            sys.stdout.write(cycle_line(cyc, a.gens))
+            sys.stdout.flush()
         rec.update(sim.describe())
         rec.update({"read_ms": read_ms, "write_ms": write_ms, "width": a.width, "height": a.height})
         write_json(a.metrics_json, rec)

@@ -40,6 +40,8 @@ class LifeConfig:
     rule: str = "B3/S23"        # Life-like rule: B<digits>/S<digits> or a name of gol_amd.RULES (no B0)
     boundary: str = "torus"     # torus | dead: the grid wraps, or is a bounded plane whose outside is always dead
     census: bool = False        # every run also returns the live cells of every generation (RunReport.population)
+    fingerprint: bool = False   # every run also returns a 64-bit grid fingerprint of every generation
+                                # (RunReport.fingerprint): the series Simulation.find_cycle searches
     decomp: str = "auto"        # auto | PxQ
     tmax: int = 0               # generations per kernel launch (0 = the backend's choice: bits 12 adder /
                                 # 16 DPP; u8 32 / 24 / 16 by tile size)
@@ -77,6 +79,7 @@ class LifeConfig:
         c.rule = str(self.rule)
         c.boundary = str(self.boundary)
         c.census = bool(self.census)
+        c.fingerprint = bool(self.fingerprint)
         c.decomp = self.decomp
         c.gen_limit = int(self.gen_limit)
         c.check_similarity = bool(self.check_similarity)
@@ -179,15 +182,53 @@ class RunReport:
     # LifeConfig.census: live cells of the whole grid (summed over ranks) at every generation
     # the run advanced through, entry i for generation g0 + 1 + i; empty when the census is off.
     population: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, dtype=np.int64), compare=False)
+    # LifeConfig.fingerprint: the grid fingerprint (gol_amd.grid_fingerprint) of the same generations,
+    # uint64; empty when off.
+    fingerprint: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, dtype=np.uint64), compare=False)
 
     @property
     def cell_updates_per_s(self) -> float:
         return self.cells * self.executed / (self.loop_ms * 1e-3) if self.loop_ms > 0 else 0.0
 
     def as_dict(self) -> dict[str, Any]:
-        d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if f.name != "population"}
+        d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)
+             if f.name not in ("population", "fingerprint")}
         d["cell_updates_per_s"] = self.cell_updates_per_s
         return d
+
+
+@dataclasses.dataclass
+class CycleReport:
+    """What ``Simulation.find_cycle`` found.  ``period`` and ``generation`` are
+    exact: confirmed by comparing the cells of two generations.
+    ``repeats_from`` is fingerprint evidence."""
+
+    period: int             # the cycle's minimal period; 0: none found up to the limit
+    generation: int         # a generation confirmed to lie on the cycle; where the simulation stopped
+    # The earliest generation since the call began from which the fingerprints repeat with
+    # ``period``: a lower bound on the generation the grid entered the cycle at, and equal to it
+    # unless two different grids of the transient have one fingerprint.  -1 with period 0.
+    repeats_from: int
+    confirmations: int      # exact comparisons that found the repeat (0 or 1)
+    false_candidates: int   # candidate periods that an exact comparison rejected
+    stop_reason: str        # cycle | limit | extinction
+    loop_ms: float = 0.0
+    # The fingerprints of the generations the call advanced through, as RunReport.fingerprint.
+    fingerprint: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, dtype=np.uint64), compare=False)
+
+    def as_dict(self) -> dict[str, Any]:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if f.name != "fingerprint"}
+
+
+def grid_fingerprint(grid: np.ndarray) -> int:
+    """The 64-bit fingerprint of an H x W grid of cells (0/1 or ASCII), on the
+    host: ``sum word(y, j) * r(y) * A(j) mod 2**64`` over the grid's 32-cell
+    words (csrc/include/gol/fingerprint.hpp).  Equal grids have equal
+    fingerprints; unequal grids may collide."""
+    g = np.ascontiguousarray(grid, dtype=np.uint8)
+    if g.ndim != 2:
+        raise ValueError("grid_fingerprint: expected a 2-D array")
+    return int(native().grid_fingerprint(g))
 
 
 class Simulation:
@@ -253,6 +294,7 @@ class Simulation:
         return {"backend": self.backend.name(), "transport": self.transport.name(),
                 "layout": self.config.resolved_layout(), "rule": self._eng.config.rule,
                 "boundary": self._eng.config.boundary, "census": bool(self._eng.config.census),
+                "fingerprint": bool(self._eng.config.fingerprint),
                 "decomp": d.describe(),
                 "rank": self.rank, "ranks": d.nranks(), "tile_rows": g.H, "tile_cols": g.W,
                 "halo_rows": g.Dv, "halo_words": g.hw, "tmax": self._eng.tmax,
@@ -340,6 +382,14 @@ class Simulation:
             ck = self.backend.census_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
             if ck:
                 parts.append(f"census kernels: {ck}")
+        if e.config.fingerprint:
+            # The fingerprint kernels: scheduled like the census kernels.
+            parts.append("fingerprint (per-generation 64-bit grid fingerprints fused into the temporal blocks; no "
+                         "linked or chained launches, no skipping, no lazy tail, no folded strip)")
+            fk = self.backend.fingerprint_kernel(native().Layout.Bits if lay == "bits" or e.via_bits
+                                                 else native().Layout.U8)
+            if fk:
+                parts.append(f"fingerprint kernels: {fk}")
         return ", ".join(parts)
 
     # -- state -----------------------------------------------------------
@@ -369,6 +419,12 @@ class Simulation:
     def alive_count(self) -> int:
         return int(self._eng.alive_count())
 
+    def fingerprint(self) -> int:
+        """The fingerprint of the current grid (``grid_fingerprint`` of the whole
+        grid): computed on the tiles and summed over ranks, so every rank of a
+        distributed run calls it."""
+        return int(self._eng.fingerprint())
+
     # -- running ---------------------------------------------------------
     def _report(self, r) -> RunReport:
         rep = RunReport(generations=r.generations, executed=r.executed, stop_reason=r.stop_reason,
@@ -378,7 +434,8 @@ class Simulation:
                         graph_launches=r.graph_launches, halo_bytes=r.halo_bytes,
                         linked_launches=r.linked_launches, phase_timed=r.phase_timed,
                         compute_ms=r.compute_ms, halo_ms=r.halo_ms, fill_ms=r.fill_ms,
-                        allreduce_ms=r.allreduce_ms, population=np.asarray(r.population, dtype=np.int64))
+                        allreduce_ms=r.allreduce_ms, population=np.asarray(r.population, dtype=np.int64),
+                        fingerprint=np.asarray(r.fingerprint, dtype=np.uint64))
         self.last_report = rep
         return rep
 
@@ -389,6 +446,21 @@ class Simulation:
     def advance(self, n: int) -> RunReport:
         """Evolve exactly ``n`` generations (no early stop)."""
         return self._report(self._eng.advance(int(n)))
+
+    def find_cycle(self, max_gens: int, max_period: int = 64, chunk: int = 0) -> CycleReport:
+        """Run until the grid repeats with a period of at most ``max_period``, or
+        to generation ``max_gens`` (needs ``LifeConfig(fingerprint=True)``).
+        Runs in chunks of ``chunk`` generations (0: 256), searches the
+        fingerprint series after each and confirms every candidate on the cells,
+        so ``period`` (the minimal one) and ``generation`` are exact;
+        ``repeats_from`` is read off the fingerprints.  A grid that stops
+        changing is period 1 (``stop_reason`` ``extinction`` if it is empty).
+        Every rank of a distributed run calls it."""
+        r = self._eng.find_cycle(int(max_gens), int(max_period), int(chunk))
+        return CycleReport(period=int(r.period), generation=int(r.generation), repeats_from=int(r.repeats_from),
+                           confirmations=int(r.confirmations), false_candidates=int(r.false_candidates),
+                           stop_reason=str(r.stop_reason), loop_ms=float(r.loop_ms),
+                           fingerprint=np.asarray(r.fingerprint, dtype=np.uint64))
 
 
 def simulate(grid: np.ndarray, gens: int, engine: str = "auto", layout: str = "auto",
@@ -406,18 +478,22 @@ def simulate(grid: np.ndarray, gens: int, engine: str = "auto", layout: str = "a
 
 def reference_run(grid: np.ndarray, gen_limit: int = 1000, check_similarity: bool = True,
                   sim_freq: int = 3, threads: int = 1, rule: str = DEFAULT_RULE,
-                  boundary: str = DEFAULT_BOUNDARY, census: bool = False):
+                  boundary: str = DEFAULT_BOUNDARY, census: bool = False, fingerprint: bool = False):
     """Exact eager serial loop of src/game.c (native), under any Life-like
     ``rule`` without B0, on the torus or (``boundary="dead"``) the bounded
     plane.  Returns (grid, gens, ms); with ``census=True`` (grid, gens, ms,
     population), population[i] the live cells of generation 1 + i (int64,
-    ``gens`` entries)."""
+    ``gens`` entries); with ``fingerprint=True`` one more entry, the grid
+    fingerprints of the same generations (uint64)."""
     r = native().cpu_reference_run(np.ascontiguousarray(grid, dtype=np.uint8), int(gen_limit),
                                    bool(check_similarity), int(sim_freq), int(threads), str(rule),
-                                   str(boundary), bool(census))
+                                   str(boundary), bool(census), bool(fingerprint))
+    out = [r[2], int(r[0]), float(r[1])]
     if census:
-        return r[2], int(r[0]), float(r[1]), np.asarray(r[3], dtype=np.int64)
-    return r[2], int(r[0]), float(r[1])
+        out.append(np.asarray(r[3], dtype=np.int64))
+    if fingerprint:
+        out.append(np.asarray(r[-1], dtype=np.uint64))
+    return tuple(out)
 
 
 def timed(fn, *a, **kw):

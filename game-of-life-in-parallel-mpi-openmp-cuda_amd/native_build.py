@@ -43,6 +43,7 @@ LIFE_VARIANTS = ["bits_w1_dpp", "bits_w1_add", "u8_w1_dpp", "u8_w1_add",
                  "bits_w1_dpp_quiet",  # quiet-tile skipping kernel (life_quiet_impl.hpp)
                  "plane_bits_dpp", "plane_u8_dpp",  # bounded plane (lb::PlaneIO)
                  "census_bits_dpp", "census_u8_dpp",  # per-generation population census (lb::CensusIO)
+                 "fprint_bits_dpp", "fprint_u8_dpp",  # per-generation grid fingerprint (lb::FingerprintIO)
                  *[f"u8_w1_dpp_t{t}" for t in (24, 32)]]  # deep byte passes
 # Life-like rules besides B3/S23: the names of csrc/kernels/life_rules.def,
 # three one-line translation units each (bit layout with the DPP and the

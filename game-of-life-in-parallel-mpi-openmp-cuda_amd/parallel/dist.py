@@ -140,7 +140,8 @@ def torch_transport(backend_obj, group=None):
                 return
 
     def allreduce_sum(addr, n, stream_ptr):
-        # The census series: 64-bit counts, far below 2^63, summed as int64.
+        # The census series (64-bit counts, far below 2^63) and the fingerprint series (sums
+        # modulo 2^64): both summed as int64, whose two's-complement addition is that sum.
         with _stream_ctx(stream_ptr):
             t = tensor_view(addr, 8 * n, on_dev, dtype="i8")
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)

@@ -77,6 +77,12 @@ class InProcessGroup:
     def advance(self, n: int) -> list[RunReport]:
         return self.parallel(lambda s: s.advance(n))
 
+    def fingerprint(self) -> list[int]:
+        return self.parallel(lambda s: s.fingerprint())
+
+    def find_cycle(self, max_gens: int, max_period: int = 64, chunk: int = 0) -> list:
+        return self.parallel(lambda s: s.find_cycle(max_gens, max_period, chunk))
+
     def gather(self) -> np.ndarray:
         out = np.zeros((self.config.height, self.config.width), dtype=np.uint8)
         for s in self.sims:

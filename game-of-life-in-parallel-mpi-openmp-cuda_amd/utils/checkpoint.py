@@ -111,6 +111,9 @@ def save_checkpoint(sim: Simulation, directory: str, is_root: bool = True, barri
     # per run and is not checkpointed.
     if cfg.census:
         meta = {k: v for k, v in meta.items() if k != "grid"} | {"census": True, "grid": name}
+    # "fingerprint" likewise.
+    if cfg.fingerprint:
+        meta = {k: v for k, v in meta.items() if k != "grid"} | {"fingerprint": True, "grid": name}
     grid = d / name
     if is_root:
         from .io import create_text_file  # noqa: PLC0415
@@ -156,7 +159,8 @@ def load_checkpoint(directory: str, **overrides) -> tuple[LifeConfig, Path]:
                      layout=meta.get("layout", "auto"), start_gen=meta["generation"],
                      sim_phase=meta["sim_phase"], rule=parse_rule(meta.get("rule", DEFAULT_RULE)),
                      boundary=_boundary(meta.get("boundary", DEFAULT_BOUNDARY)),
-                     census=bool(meta.get("census", False)))
+                     census=bool(meta.get("census", False)),
+                     fingerprint=bool(meta.get("fingerprint", False)))
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg, d / _meta_grid(meta, d)
@@ -170,6 +174,7 @@ def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], 
     eng = sim.native_engine
     total_ms, executed, exch, polls, launches = 0.0, 0, 0, 0, 0
     population = []  # LifeConfig.census: the chunks' series concatenate to the whole run's
+    fingerprint = []  # LifeConfig.fingerprint: likewise
     while True:
         target = min(limit, sim.generation + every) if every > 0 else limit
         r = eng.run_until(target)
@@ -179,10 +184,12 @@ def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], 
         polls += r.polls
         launches += r.kernel_launches
         population.append(np.asarray(r.population, dtype=np.int64))
+        fingerprint.append(np.asarray(r.fingerprint, dtype=np.uint64))
         if r.first_unchanged >= 0 or sim.generation >= limit:
             gens, reason = reported_generations(r.first_unchanged, r.extinct, limit, cfg.start_gen,
                                                 cfg.check_similarity, cfg.sim_freq, cfg.sim_phase)
             return RunReport(gens, executed, reason, total_ms, r.first_unchanged, r.extinct, exch,
-                             polls, launches, cfg.width * cfg.height, population=np.concatenate(population))
+                             polls, launches, cfg.width * cfg.height, population=np.concatenate(population),
+                             fingerprint=np.concatenate(fingerprint))
         if directory:
             save_checkpoint(sim, directory, is_root, barrier)
