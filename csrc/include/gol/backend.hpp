@@ -8,6 +8,7 @@
 //                   (epochs, halos, lazy termination) be tested without a GPU.
 #pragma once
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <string>
@@ -17,6 +18,24 @@
 #include "gol/tuning.hpp"
 
 namespace gol {
+
+// The part of the global rectangle (x, y, w, h) that falls in the owned cells
+// of a tile whose first owned row and cell are global (global_row0,
+// global_col0): hh x ww cells from owned row r0, owned cell c0 on, which are
+// row wy, column wx of the rectangle.
+struct WindowClip {
+  int64_t r0 = 0, c0 = 0, wy = 0, wx = 0, h = 0, w = 0;
+  bool empty() const { return h <= 0 || w <= 0; }
+};
+inline WindowClip clip_window(const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x, int64_t y,
+                              int64_t w, int64_t h) {
+  GOL_REQUIRE(w > 0 && h > 0 && w <= (int64_t(1) << 26) / h, "window: an empty rectangle or more than 2^26 cells");
+  const int64_t ya = std::max(y, global_row0), yb = std::min(y + h, global_row0 + g.H);
+  const int64_t xa = std::max(x, global_col0), xb = std::min(x + w, global_col0 + g.W);
+  WindowClip c;
+  c.r0 = ya - global_row0, c.c0 = xa - global_col0, c.wy = ya - y, c.wx = xa - x, c.h = yb - ya, c.w = xb - xa;
+  return c;
+}
 
 class Backend {
  public:
@@ -271,6 +290,33 @@ class Backend {
   // *flag (backend memory, zeroed by the caller; stream-ordered) = 1 if any
   // owned cell of two tiles of geometry g differs.
   virtual void tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) = 0;
+  // View operations (kernels/view_ops.hip).  Coordinates are global: owned
+  // row 0 of the tile is global row global_row0, its first owned cell global
+  // cell global_col0 (any value, not only multiples of 32); only owned rows
+  // and cells are read or written.  Stream-ordered on the compute stream.
+  //
+  // density: adds, for every global block of by x bx cells (block (i, j):
+  // global rows [i*by, (i+1)*by), cells [j*bx, (j+1)*bx), clipped at the grid
+  // of grid_h x grid_w cells), the live owned cells of the tile inside it to
+  // out[i * ceil(grid_w / bx) + j] (backend memory, zeroed by the caller).
+  virtual void density(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t grid_h,
+                       int64_t grid_w, int64_t bx, int64_t by, uint64_t* out) = 0;
+  // store_window: the owned cells of the global rectangle (x, y, w, h) that
+  // fall in the tile, into the h x w host array `cells` at their place in the
+  // window ('0'/'1' when ascii else 0/1); the rest of `cells` is left alone.
+  // Synchronous, through the bounded staging buffer like store_owned.
+  virtual void store_window(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x,
+                            int64_t y, int64_t w, int64_t h, uint8_t* cells, bool ascii) = 0;
+  // place_window: the part of the h x w host array `cells` (1 or '1': alive)
+  // at global (x, y) that falls in the tile, written into it.  mode kPlaceCopy
+  // overwrites the rectangle, kPlaceOr adds its live cells.  Synchronous.
+  static constexpr int kPlaceCopy = 0, kPlaceOr = 1;
+  virtual void place_window(void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x,
+                            int64_t y, int64_t w, int64_t h, const uint8_t* cells, int mode) = 0;
+  // Limits of the view operations: output blocks of a density map, cells of
+  // a window or a stamp.
+  static constexpr int64_t kDensityBlocksMax = int64_t(1) << 24;
+  static constexpr int64_t kWindowCellsMax = int64_t(1) << 26;
   // Host <-> tile conversion: `cells` is an H x W array of bytes (ld = row
   // stride); load treats byte == '1' or byte == 1 as alive; store writes
   // '0'/'1' when ascii else 0/1.

@@ -299,6 +299,27 @@ class Engine {
   // every rank calls it.  Any engine, whatever EngineConfig::fingerprint says
   // (the HIP backend needs tiles that start on a multiple of 32 columns).
   uint64_t fingerprint();
+  // Views of the current grid (Backend::density / store_window / place_window).
+  // Every rank calls each of them with the same arguments; coordinates are
+  // global and in the true frame (a drifted frame is rotated back first), and
+  // a rectangle must lie inside the grid (no wrap, on either boundary).
+  //
+  // The population of every by x bx block of the grid, row-major, ceil(H/by)
+  // x ceil(W/bx) blocks (at most Backend::kDensityBlocksMax), clipped at the
+  // grid's edge; the same on every rank.  Reduced on the device over the tile
+  // that holds the state (the bit image of a byte engine on bit words).
+  std::vector<uint64_t> density(int64_t bx, int64_t by);
+  // The same into caller memory of ceil(H/by) * ceil(W/bx) entries (checked
+  // against the limit before anything is written).
+  void density(int64_t bx, int64_t by, uint64_t* out);
+  // The h x w cells at (x, y) into `cells` (dense, h x w; '0'/'1' when ascii
+  // else 0/1), complete on every rank; w * h <= Backend::kWindowCellsMax.
+  void store_window(int64_t x, int64_t y, int64_t w, int64_t h, uint8_t* cells, bool ascii);
+  // Writes the dense h x w array `cells` (1 or '1': alive) into the grid at
+  // (x, y), leaving the rest of the grid as it is: mode Backend::kPlaceCopy
+  // overwrites the rectangle, kPlaceOr adds its live cells.  The generation
+  // number stays.
+  void place(int64_t x, int64_t y, int64_t w, int64_t h, const uint8_t* cells, int mode);
 
   // Runs from the current generation up to config().gen_limit with the
   // reference's termination semantics.
@@ -512,6 +533,12 @@ class Engine {
   Owned<uint64_t> fprint_;
   bool fprint_run_ = false;
   Owned<uint64_t> fp_dev_;
+  // density()'s block map and store_window()'s window on the device (the
+  // latter on multi-rank runs only), kept between calls and re-allocated
+  // when a call needs more (density_len_) or another size (window_len_).
+  Owned<uint64_t> density_dev_, density_host_, window_dev_;  // density_host_: the map's pinned mirror
+  size_t density_len_ = 0, window_len_ = 0;
+  void require_rect(const char* what, int64_t x, int64_t y, int64_t w, int64_t h) const;
   Owned<> snap_;
   size_t snap_bytes_ = 0;
   bool differs_from_snapshot();

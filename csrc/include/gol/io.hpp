@@ -54,4 +54,31 @@ inline void write_text_grid(const std::string& path, int64_t W, int64_t H, const
 void generate_text_file(const std::string& path, int64_t W, int64_t H, uint64_t seed,
                         double density);
 
+// Run-length encoded pattern files (the RLE dialect of Life pattern
+// collections): '#' comment lines, the header "x = W, y = H[, rule = R]", then
+// runs <count><tag> with tags b (dead), o (alive), $ (end of row) and ! (end of
+// pattern), broken into lines anywhere.  Rows shorter than W and rows missing
+// at the end are dead.
+struct RlePattern {
+  std::vector<uint8_t> cells;  // h x w bytes of 0/1
+  int64_t w = 0, h = 0;
+  std::string rule;            // the header's rule text as written, "" if absent
+};
+// Throws gol::Error naming the line (counted from 1) on any other tag, a row or
+// column beyond the header's size, a missing header or '!', and on patterns of
+// more than 2^26 cells.
+RlePattern parse_rle(const std::string& text);
+// The same dialect, lines of at most 70 characters; parse_rle(format_rle(a))
+// gives back a.  rule "" writes no rule.
+std::string format_rle(const uint8_t* cells, int64_t w, int64_t h, const std::string& rule);
+
+
+// Grey image of a density map (Engine::density): a block of n cells (clipped at
+// the grid's edge) with c live ones is 0 if c == 0, else max(1, (255 c + n/2) /
+// n), so a single live cell in a large block still shows.  Row-major,
+// ceil(H/by) x ceil(W/bx) pixels.
+std::vector<uint8_t> density_image(const uint64_t* counts, int64_t by, int64_t bx, int64_t H, int64_t W);
+// Binary PGM (P5, maxval 255) of a w x h image.
+void write_pgm(const std::string& path, const uint8_t* image, int64_t w, int64_t h);
+
 }  // namespace gol

@@ -493,5 +493,18 @@ void launch_copy_owned_rows(const uint8_t* src, uint8_t* dst, const TileGeom& g,
 // Sets *flag to 1 if any owned cell of two tiles of geometry g differs.
 void launch_equal(const uint8_t* a, const uint8_t* b, const TileGeom& g, uint32_t* flag, hipStream_t s);
 
+// View kernels (view_ops.hip; Backend::density / store_window / place_window).
+// Adds the live owned cells of the tile to the global by x bx block map `out`
+// (row-major, ceil(grid_w / bx) blocks per row); owned row 0 is global row
+// global_row0, the first owned cell global cell global_col0.  Either layout.
+void launch_density(const uint8_t* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t grid_h,
+                    int64_t grid_w, int64_t bx, int64_t by, unsigned long long* out, hipStream_t s);
+// The hh x ww owned cells from owned row r0, owned cell c0 on, into / from a
+// dense device array of hh x ww bytes.
+void launch_store_window(const uint8_t* buf, const TileGeom& g, int64_t r0, int64_t c0, int64_t ww, int64_t hh,
+                         uint8_t* stage, bool ascii, hipStream_t s);
+void launch_place_window(uint8_t* buf, const TileGeom& g, int64_t r0, int64_t c0, int64_t ww, int64_t hh,
+                         const uint8_t* stage, bool copy, hipStream_t s);
+
 }  // namespace hipk
 }  // namespace gol

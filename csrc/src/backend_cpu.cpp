@@ -287,6 +287,12 @@ class CpuBackend final : public Backend {
     *flag = alive_count(buf, g) > 0 ? 1u : 0u;
   }
   int64_t alive_count(const void* buf, const TileGeom& g) override;
+  void density(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t grid_h,
+               int64_t grid_w, int64_t bx, int64_t by, uint64_t* out) override;
+  void store_window(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x, int64_t y,
+                    int64_t w, int64_t h, uint8_t* cells, bool ascii) override;
+  void place_window(void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x, int64_t y,
+                    int64_t w, int64_t h, const uint8_t* cells, int mode) override;
   void load_owned(void* buf, const TileGeom& g, const uint8_t* cells, int64_t ld) override;
   void store_owned(const void* buf, const TileGeom& g, uint8_t* cells, int64_t ld,
                    bool ascii) override;
@@ -620,6 +626,69 @@ int64_t CpuBackend::alive_count(const void* buf, const TileGeom& g) {
   int64_t s = 0;
   for (auto v : part) s += v;
   return s;
+}
+
+// The view operations, cell by cell: the second witness of the HIP kernels
+// (kernels/view_ops.hip).
+namespace {
+inline bool owned_cell(const uint8_t* row, const TileGeom& g, int64_t x) {
+  if (g.layout == Layout::Bits)
+    return (reinterpret_cast<const uint32_t*>(row)[g.hw + x / 32] >> (x % 32)) & 1u;
+  return row[g.cell0() + x] != 0;
+}
+}  // namespace
+
+void CpuBackend::density(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t grid_h,
+                         int64_t grid_w, int64_t bx, int64_t by, uint64_t* out) {
+  GOL_REQUIRE(bx >= 1 && by >= 1, "density: block sizes must be at least 1");
+  GOL_REQUIRE(global_row0 >= 0 && global_col0 >= 0 && global_row0 + g.H <= grid_h && global_col0 + g.W <= grid_w,
+              "density: the tile leaves the grid");
+  const int64_t nbx = ceil_div(grid_w, bx), nby = ceil_div(grid_h, by);
+  GOL_REQUIRE(nbx <= kDensityBlocksMax && nby <= kDensityBlocksMax && nbx * nby <= kDensityBlocksMax,
+              "density: more than 2^24 blocks");
+  auto* p = static_cast<const uint8_t*>(buf);
+  for (int64_t i = 0; i < g.H; ++i) {
+    const uint8_t* row = p + (g.row0() + i) * g.pitch;
+    uint64_t* orow = out + ((global_row0 + i) / by) * nbx;
+    for (int64_t x = 0; x < g.W; ++x)
+      if (owned_cell(row, g, x)) ++orow[(global_col0 + x) / bx];
+  }
+}
+
+void CpuBackend::store_window(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x,
+                              int64_t y, int64_t w, int64_t h, uint8_t* cells, bool ascii) {
+  const WindowClip c = clip_window(g, global_row0, global_col0, x, y, w, h);
+  if (c.empty()) return;
+  auto* p = static_cast<const uint8_t*>(buf);
+  const uint8_t base = ascii ? '0' : 0;
+  for (int64_t i = 0; i < c.h; ++i) {
+    const uint8_t* row = p + (g.row0() + c.r0 + i) * g.pitch;
+    uint8_t* dst = cells + (c.wy + i) * w + c.wx;
+    for (int64_t j = 0; j < c.w; ++j) dst[j] = uint8_t(base + owned_cell(row, g, c.c0 + j));
+  }
+}
+
+void CpuBackend::place_window(void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x,
+                              int64_t y, int64_t w, int64_t h, const uint8_t* cells, int mode) {
+  GOL_REQUIRE(mode == kPlaceCopy || mode == kPlaceOr, "place_window: unknown mode");
+  const WindowClip c = clip_window(g, global_row0, global_col0, x, y, w, h);
+  if (c.empty()) return;
+  auto* p = static_cast<uint8_t*>(buf);
+  for (int64_t i = 0; i < c.h; ++i) {
+    uint8_t* row = p + (g.row0() + c.r0 + i) * g.pitch;
+    const uint8_t* src = cells + (c.wy + i) * w + c.wx;
+    for (int64_t j = 0; j < c.w; ++j) {
+      const bool v = src[j] == 1 || src[j] == '1';
+      if (!v && mode == kPlaceOr) continue;
+      const int64_t cx = c.c0 + j;
+      if (g.layout == Layout::Bits) {
+        uint32_t& word = reinterpret_cast<uint32_t*>(row)[g.hw + cx / 32];
+        word = (word & ~(1u << (cx % 32))) | (uint32_t(v) << (cx % 32));
+      } else {
+        row[g.cell0() + cx] = uint8_t(v);
+      }
+    }
+  }
 }
 
 void CpuBackend::load_owned(void* buf, const TileGeom& g, const uint8_t* cells, int64_t ld) {

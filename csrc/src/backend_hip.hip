@@ -1054,6 +1054,44 @@ class HipBackend final : public Backend {
                              reinterpret_cast<unsigned long long*>(out64), stream_);
     HIP_CHECK(hipGetLastError());
   }
+  void density(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t grid_h,
+               int64_t grid_w, int64_t bx, int64_t by, uint64_t* out) override {
+    join_streams();
+    GOL_ON_DEVICE();
+    hipk::launch_density(static_cast<const uint8_t*>(buf), g, global_row0, global_col0, grid_h, grid_w, bx, by,
+                         reinterpret_cast<unsigned long long*>(out), stream_);
+    HIP_CHECK(hipGetLastError());
+  }
+  // Windows go through the staging buffer like whole tiles (store_owned); a
+  // window is at most Backend::kWindowCellsMax bytes there, so one piece.
+  void store_window(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x, int64_t y,
+                    int64_t w, int64_t h, uint8_t* cells, bool ascii) override {
+    join_streams();
+    GOL_ON_DEVICE();
+    const WindowClip c = clip_window(g, global_row0, global_col0, x, y, w, h);
+    if (c.empty()) return;
+    uint8_t* stage = static_cast<uint8_t*>(stage_buf(c.h * c.w));
+    hipk::launch_store_window(static_cast<const uint8_t*>(buf), g, c.r0, c.c0, c.w, c.h, stage, ascii, stream_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy2DAsync(cells + c.wy * w + c.wx, size_t(w), stage, size_t(c.w), size_t(c.w), size_t(c.h),
+                               hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+  void place_window(void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0, int64_t x, int64_t y,
+                    int64_t w, int64_t h, const uint8_t* cells, int mode) override {
+    GOL_REQUIRE(mode == kPlaceCopy || mode == kPlaceOr, "place_window: unknown mode");
+    quiet_invalidate();
+    join_streams();
+    GOL_ON_DEVICE();
+    const WindowClip c = clip_window(g, global_row0, global_col0, x, y, w, h);
+    if (c.empty()) return;
+    uint8_t* stage = static_cast<uint8_t*>(stage_buf(c.h * c.w));
+    HIP_CHECK(hipMemcpy2DAsync(stage, size_t(c.w), cells + c.wy * w + c.wx, size_t(w), size_t(c.w), size_t(c.h),
+                               hipMemcpyHostToDevice, stream_));
+    hipk::launch_place_window(static_cast<uint8_t*>(buf), g, c.r0, c.c0, c.w, c.h, stage, mode == kPlaceCopy, stream_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
   void copy_owned_rows(void* dst, const void* src, const TileGeom& g) override {
     join_streams();
     GOL_ON_DEVICE();

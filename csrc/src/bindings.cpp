@@ -433,6 +433,46 @@ PYBIND11_MODULE(_gol, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("alive_count", &Engine::alive_count, py::call_guard<py::gil_scoped_release>())
       .def("fingerprint", &Engine::fingerprint, py::call_guard<py::gil_scoped_release>())
+      // Views (Engine::density / store_window / place): global coordinates,
+      // every rank calls them.
+      .def("density",
+           [](Engine& e, int64_t bx, int64_t by) {
+             GOL_REQUIRE(bx >= 1 && by >= 1, "density: block sizes must be at least 1");
+             const int64_t nby = ceil_div(e.decomp().H, by), nbx = ceil_div(e.decomp().W, bx);
+             const bool fits = nbx <= Backend::kDensityBlocksMax && nby <= Backend::kDensityBlocksMax &&
+                               nbx * nby <= Backend::kDensityBlocksMax;
+             py::array_t<int64_t> a({fits ? nby : 0, fits ? nbx : 0});  // the engine refuses the rest by name
+             auto* out = reinterpret_cast<uint64_t*>(a.mutable_data());
+             {
+               py::gil_scoped_release rel;
+               e.density(bx, by, out);
+             }
+             return a;
+           },
+           py::arg("bx"), py::arg("by"))
+      .def("store_window",
+           [](Engine& e, int64_t x, int64_t y, int64_t w, int64_t h, bool ascii) {
+             // The engine checks the rectangle before it touches the array.
+             const bool fits = w >= 1 && h >= 1 && w <= Backend::kWindowCellsMax / h;
+             std::vector<uint8_t> v(fits ? size_t(w * h) : 0);
+             {
+               py::gil_scoped_release rel;
+               e.store_window(x, y, w, h, v.data(), ascii);
+             }
+             return to_array(std::move(v), h, w);
+           },
+           py::arg("x"), py::arg("y"), py::arg("w"), py::arg("h"), py::arg("ascii") = false)
+      .def("place",
+           [](Engine& e, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, int64_t x, int64_t y,
+              const std::string& mode) {
+             GOL_REQUIRE(a.ndim() == 2, "place: expected a 2-D array of cells");
+             GOL_REQUIRE(mode == "copy" || mode == "or", "place: mode '" + mode + "' (want copy or or)");
+             const int64_t h = a.shape(0), w = a.shape(1);
+             const uint8_t* p = a.data();
+             py::gil_scoped_release rel;
+             e.place(x, y, w, h, p, mode == "or" ? Backend::kPlaceOr : Backend::kPlaceCopy);
+           },
+           py::arg("cells"), py::arg("x"), py::arg("y"), py::arg("mode") = "copy")
       .def("find_cycle", &Engine::find_cycle, py::arg("max_gens"), py::arg("max_period") = 64, py::arg("chunk") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("run", &Engine::run, py::call_guard<py::gil_scoped_release>())
@@ -582,6 +622,19 @@ PYBIND11_MODULE(_gol, m) {
     py::gil_scoped_release rel;
     write_text_grid(path, W, H, p);
   });
+  m.def("parse_rle", [](const std::string& text) {
+    RlePattern p = parse_rle(text);
+    const int64_t h = p.h, w = p.w;
+    return py::make_tuple(to_array(std::move(p.cells), h, w), p.rule);
+  });
+  m.def("format_rle",
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, const std::string& rule) {
+          GOL_REQUIRE(a.ndim() == 2, "expected a 2-D array");
+          return format_rle(a.data(), a.shape(1), a.shape(0), rule);
+        },
+        py::arg("cells"), py::arg("rule") = "B3/S23");
+  m.attr("DENSITY_BLOCKS_MAX") = Backend::kDensityBlocksMax;
+  m.attr("WINDOW_CELLS_MAX") = Backend::kWindowCellsMax;
   m.def("generate_text_file", &generate_text_file, py::arg("path"), py::arg("W"), py::arg("H"),
         py::arg("seed") = 1, py::arg("density") = 0.5, py::call_guard<py::gil_scoped_release>());
   m.def("random_grid", [](int64_t W, int64_t H, uint64_t seed, double density) {

@@ -386,6 +386,111 @@ uint64_t Engine::fingerprint() {
   return f;
 }
 
+// ---- views --------------------------------------------------------------------
+// Each prepares the grid like the existing call it resembles:
+//   * settle_pending: a triggered halo exchange may still be writing the
+//     buffers (invalidating it where the grid is about to change);
+//   * replay_tail: a lazy tail left the block chain ahead of generation();
+//   * sync_bytes: windows read and write the byte tile, so a live bit image is
+//     unpacked first (density reads the image itself instead);
+//   * normalize: coordinates are true ones, the stored frame may be drifted.
+std::vector<uint64_t> Engine::density(int64_t bx, int64_t by) {
+  GOL_REQUIRE(bx >= 1 && by >= 1, "density: block sizes must be at least 1");
+  const int64_t nbx = ceil_div(cfg_.W, bx), nby = ceil_div(cfg_.H, by);
+  const bool fits = nbx <= Backend::kDensityBlocksMax && nby <= Backend::kDensityBlocksMax &&
+                    nbx * nby <= Backend::kDensityBlocksMax;
+  std::vector<uint64_t> out(fits ? size_t(nbx * nby) : 0);  // too many: refused below, by name
+  density(bx, by, out.data());
+  return out;
+}
+
+void Engine::density(int64_t bx, int64_t by, uint64_t* out) {
+  GOL_REQUIRE(bx >= 1 && by >= 1, "density: block sizes must be at least 1 (got " + std::to_string(by) + "x" +
+                                      std::to_string(bx) + ")");
+  const int64_t nbx = ceil_div(cfg_.W, bx), nby = ceil_div(cfg_.H, by);
+  GOL_REQUIRE(nbx <= Backend::kDensityBlocksMax && nby <= Backend::kDensityBlocksMax &&
+                  nbx * nby <= Backend::kDensityBlocksMax,
+              "density: " + std::to_string(nby) + " x " + std::to_string(nbx) + " blocks of " + std::to_string(by) +
+                  "x" + std::to_string(bx) + " cells are more than 2^24; use larger blocks");
+  settle_pending(false);
+  replay_tail();
+  if (drift_ != 0) normalize();  // a block is a range of true columns
+  const Tile s = state_tile();
+  const size_t n = size_t(nbx * nby);
+  if (!density_dev_ || density_len_ < n) {  // kept while it is large enough: a movie may alternate block sizes
+    density_dev_.reset();
+    density_host_.reset();
+    density_dev_ = Owned<uint64_t>(be_, be_->alloc(n * 8));
+    density_host_ = Owned<uint64_t>(be_, be_->alloc_host(n * 8), /*host=*/true);
+    density_len_ = n;
+  }
+  be_->join_streams();
+  be_->memset_async(density_dev_, 0, n * 8);
+  be_->density(s.cur(), s.g, rows().begin, cols().begin, cfg_.H, cfg_.W, bx, by, density_dev_);
+  if (tr_->size() > 1) tr_->allreduce_sum_u64(density_dev_, n, be_->stream());
+  // Through the pinned mirror: a map of a few MiB copied straight into pageable
+  // memory measured 20-30 ms per call (docs/PERFORMANCE.md).
+  be_->copy_d2h_async_on(density_host_, density_dev_, n * 8, nullptr);
+  be_->synchronize();
+  std::copy(density_host_.get(), density_host_.get() + n, out);
+}
+
+void Engine::require_rect(const char* what, int64_t x, int64_t y, int64_t w, int64_t h) const {
+  const std::string rect = "rectangle x=" + std::to_string(x) + " y=" + std::to_string(y) + " w=" + std::to_string(w) +
+                           " h=" + std::to_string(h);
+  GOL_REQUIRE(w >= 1 && h >= 1, std::string(what) + ": " + rect + " is empty");
+  GOL_REQUIRE(x >= 0 && y >= 0 && w <= cfg_.W - x && h <= cfg_.H - y,
+              std::string(what) + ": " + rect + " leaves the grid of " + std::to_string(cfg_.W) + " x " +
+                  std::to_string(cfg_.H) + " cells (windows do not wrap)");
+  GOL_REQUIRE(w <= Backend::kWindowCellsMax / h,
+              std::string(what) + ": " + rect + " has more than 2^26 cells");
+}
+
+void Engine::store_window(int64_t x, int64_t y, int64_t w, int64_t h, uint8_t* cells, bool ascii) {
+  require_rect("store_window", x, y, w, h);
+  settle_pending(false);
+  replay_tail();
+  sync_bytes();
+  normalize();
+  be_->synchronize();
+  if (tr_->size() == 1) {
+    be_->store_window(buf_[cur_], g_, rows().begin, cols().begin, x, y, w, h, cells, ascii);
+    return;
+  }
+  // The ranks' pieces are disjoint: each writes its own as 0/1 into a zeroed
+  // window, and the sum over ranks (as 64-bit words) is the whole window.
+  const size_t n = size_t(w * h), words = (n + 7) / 8;
+  std::vector<uint8_t> mine(words * 8, 0);
+  be_->store_window(buf_[cur_], g_, rows().begin, cols().begin, x, y, w, h, mine.data(), false);
+  if (!window_dev_ || window_len_ != words) {
+    window_dev_.reset();
+    window_dev_ = Owned<uint64_t>(be_, be_->alloc(words * 8));
+    window_len_ = words;
+  }
+  be_->copy_h2d(window_dev_, mine.data(), words * 8);
+  tr_->allreduce_sum_u64(window_dev_, words, be_->stream());
+  be_->synchronize();
+  be_->copy_d2h(mine.data(), window_dev_, words * 8);
+  const uint8_t base = ascii ? '0' : 0;
+  for (size_t i = 0; i < n; ++i) cells[i] = uint8_t(base + mine[i]);
+}
+
+void Engine::place(int64_t x, int64_t y, int64_t w, int64_t h, const uint8_t* cells, int mode) {
+  require_rect("place", x, y, w, h);
+  GOL_REQUIRE(mode == Backend::kPlaceCopy || mode == Backend::kPlaceOr, "place: mode must be copy or or");
+  // Like a load that keeps the rest of the grid: the byte tile becomes the
+  // state (a run packs it again), no exchange stays pending, and every epoch
+  // begins by exchanging or filling its halos (run_epoch), so none is assumed
+  // valid across the write.
+  settle_pending(true);
+  replay_tail();
+  sync_bytes();
+  normalize();
+  be_->place_window(buf_[cur_], g_, rows().begin, cols().begin, x, y, w, h, cells, mode);
+  be_->quiet_invalidate();
+  be_->synchronize();
+}
+
 // Whether the state tile differs from find_cycle's copy in any owned cell, on
 // any rank.
 bool Engine::differs_from_snapshot() {

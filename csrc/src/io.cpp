@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cstdio>
 #include <cstring>
 
 #include "gol/backend.hpp"
@@ -261,6 +262,164 @@ void generate_text_file(const std::string& path, int64_t W, int64_t H, uint64_t 
       if (!m.base) pwrite_all(f.fd, buf.data(), buf.size(), r * (W + 1), path);
     }
   }, 16);
+}
+
+// ---- RLE patterns -------------------------------------------------------------
+
+RlePattern parse_rle(const std::string& text) {
+  RlePattern p;
+  int64_t line_no = 0, last_line = 1;  // last_line: the last one that is not blank
+  bool header = false, done = false;
+  int64_t x = 0, y = 0, count = 0;
+  bool have_count = false;
+  const auto bad = [&](const std::string& why) { fail("rle: line " + std::to_string(line_no) + ": " + why); };
+  size_t pos = 0;
+  while (pos <= text.size() && !done) {
+    size_t end = text.find('\n', pos);
+    if (end == std::string::npos) end = text.size();
+    std::string line = text.substr(pos, end - pos);
+    pos = end + 1;
+    ++line_no;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    size_t i = line.find_first_not_of(" \t");
+    if (i == std::string::npos) {
+      if (pos > text.size()) break;
+      continue;
+    }
+    last_line = line_no;
+    if (line[i] == '#') continue;
+    if (!header) {
+      // x = W, y = H[, rule = R]
+      const auto number_after = [&](const char* key, int64_t* out) {
+        size_t k = line.find(key);
+        if (k == std::string::npos) return false;
+        k = line.find('=', k);
+        if (k == std::string::npos) return false;
+        k = line.find_first_not_of(" \t", k + 1);
+        if (k == std::string::npos || line[k] < '0' || line[k] > '9') return false;
+        int64_t v = 0;
+        for (; k < line.size() && line[k] >= '0' && line[k] <= '9'; ++k) {
+          v = v * 10 + (line[k] - '0');
+          if (v > (int64_t(1) << 40)) return false;
+        }
+        *out = v;
+        return true;
+      };
+      if (line[i] != 'x' || !number_after("x", &p.w) || !number_after("y", &p.h))
+        bad("expected the header 'x = W, y = H[, rule = R]', got '" + line + "'");
+      if (p.w < 1 || p.h < 1) bad("the header's size must be at least 1 x 1");
+      if (p.w > (int64_t(1) << 26) / p.h)
+        bad("a pattern of " + std::to_string(p.w) + " x " + std::to_string(p.h) + " cells is above the cap of 2^26");
+      const size_t r = line.find("rule");
+      if (r != std::string::npos) {
+        size_t k = line.find('=', r);
+        if (k == std::string::npos) bad("'rule' without '='");
+        k = line.find_first_not_of(" \t", k + 1);
+        if (k != std::string::npos) {
+          p.rule = line.substr(k);
+          while (!p.rule.empty() && (p.rule.back() == ' ' || p.rule.back() == '\t')) p.rule.pop_back();
+        }
+      }
+      p.cells.assign(size_t(p.w * p.h), 0);
+      header = true;
+      continue;
+    }
+    for (; i < line.size() && !done; ++i) {
+      const char c = line[i];
+      if (c == ' ' || c == '\t') continue;
+      if (c >= '0' && c <= '9') {
+        count = count * 10 + (c - '0');
+        have_count = true;
+        if (count > (int64_t(1) << 27)) bad("a run count is too large");
+        continue;
+      }
+      const int64_t n = have_count ? count : 1;
+      if (have_count && count == 0) bad("a run count of 0");
+      count = 0;
+      have_count = false;
+      if (c == 'b' || c == 'o') {
+        if (y >= p.h) bad("row " + std::to_string(y) + " is beyond the header's y = " + std::to_string(p.h));
+        if (x + n > p.w)
+          bad("column " + std::to_string(x + n - 1) + " is beyond the header's x = " + std::to_string(p.w));
+        if (c == 'o')
+          for (int64_t k = 0; k < n; ++k) p.cells[size_t(y * p.w + x + k)] = 1;
+        x += n;
+      } else if (c == '$') {
+        y += n;
+        x = 0;
+      } else if (c == '!') {
+        if (n != 1) bad("a run count before '!'");
+        done = true;
+      } else {
+        bad(std::string("unknown tag '") + c + "' (this reader knows b, o, $ and !)");
+      }
+    }
+    if (pos > text.size()) break;
+  }
+  if (!done) line_no = last_line;  // the text ended: name its last line
+  if (!header) bad("no header 'x = W, y = H'");
+  if (!done) bad("the pattern does not end with '!'");
+  return p;
+}
+
+std::string format_rle(const uint8_t* cells, int64_t w, int64_t h, const std::string& rule) {
+  GOL_REQUIRE(w >= 1 && h >= 1 && w <= (int64_t(1) << 26) / h, "format_rle: bad size");
+  std::string out = "x = " + std::to_string(w) + ", y = " + std::to_string(h);
+  if (!rule.empty()) out += ", rule = " + rule;
+  out += "\n";
+  std::string line;
+  const auto emit = [&](int64_t n, char tag) {
+    if (n <= 0) return;
+    const std::string item = (n > 1 ? std::to_string(n) : std::string()) + tag;
+    if (line.size() + item.size() > 70) {
+      out += line + "\n";
+      line.clear();
+    }
+    line += item;
+  };
+  int64_t pending_rows = 0;  // '$' not written yet: trailing dead rows are dropped
+  for (int64_t y = 0; y < h; ++y) {
+    const uint8_t* row = cells + y * w;
+    int64_t last = w;  // trailing dead cells of a row are dropped
+    while (last > 0 && !(row[last - 1] == 1 || row[last - 1] == '1')) --last;
+    if (last > 0) {
+      emit(pending_rows, '$');
+      pending_rows = 0;
+      for (int64_t x = 0; x < last;) {
+        const bool v = row[x] == 1 || row[x] == '1';
+        int64_t e = x;
+        while (e < last && (row[e] == 1 || row[e] == '1') == v) ++e;
+        emit(e - x, v ? 'o' : 'b');
+        x = e;
+      }
+    }
+    ++pending_rows;
+  }
+  emit(1, '!');
+  out += line + "\n";
+  return out;
+}
+
+std::vector<uint8_t> density_image(const uint64_t* counts, int64_t by, int64_t bx, int64_t H, int64_t W) {
+  GOL_REQUIRE(by >= 1 && bx >= 1 && H >= 1 && W >= 1, "density_image: bad sizes");
+  const int64_t nby = ceil_div(H, by), nbx = ceil_div(W, bx);
+  std::vector<uint8_t> img(size_t(nby * nbx));
+  for (int64_t i = 0; i < nby; ++i) {
+    const int64_t rows = std::min(by, H - i * by);
+    for (int64_t j = 0; j < nbx; ++j) {
+      const uint64_t n = uint64_t(rows * std::min(bx, W - j * bx)), c = counts[i * nbx + j];
+      img[size_t(i * nbx + j)] = c == 0 ? 0 : uint8_t(std::max<uint64_t>(1, (255 * c + n / 2) / n));
+    }
+  }
+  return img;
+}
+
+void write_pgm(const std::string& path, const uint8_t* image, int64_t w, int64_t h) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  GOL_REQUIRE(f != nullptr, "cannot write '" + path + "': " + std::strerror(errno));
+  std::fprintf(f, "P5\n%lld %lld\n255\n", (long long)w, (long long)h);
+  const bool ok = std::fwrite(image, 1, size_t(w * h), f) == size_t(w * h);
+  GOL_REQUIRE(std::fclose(f) == 0 && ok, "short write to '" + path + "'");
 }
 
 }  // namespace gol

@@ -95,7 +95,111 @@ struct Options {
   std::string resume;               // checkpoint directory to resume from
   bool gens_set = false, sim_set = false;
   Tuning tune = Tuning::from_env();  // --tune key=value over the GOL_* environment
+  // Views of huge grids: patterns stamped after the input is loaded, a density
+  // image of the final grid (and of every K-th generation), windows of it.
+  struct Place {
+    std::string file;
+    bool centred = true;
+    int64_t x = 0, y = 0;
+  };
+  struct Window {
+    int64_t x = 0, y = 0, w = 0, h = 0;
+    std::string path;
+  };
+  std::vector<Place> places;    // --place FILE[@X,Y], in the order given
+  std::vector<Window> windows;  // --window X,Y,W,H:PATH
+  std::string density_file;     // --density PATH ("": off)
+  int64_t density_by = 0, density_bx = 0;  // --density-block (0: default_density_block)
+  int64_t density_every = 0;    // --density-every K (0: the final grid only)
 };
+
+// "a,b,c" as integers; false unless exactly n of them.
+bool parse_ints(const std::string& s, size_t n, int64_t* out) {
+  size_t pos = 0;
+  for (size_t k = 0; k < n; ++k) {
+    size_t end = k + 1 < n ? s.find(',', pos) : s.size();
+    if (end == std::string::npos || end == pos) return false;
+    const std::string t = s.substr(pos, end - pos);
+    char* rest = nullptr;
+    out[k] = std::strtoll(t.c_str(), &rest, 10);
+    if (*rest != 0) return false;
+    pos = end + 1;
+  }
+  return true;
+}
+
+// The smallest power of two that gives at most 1024 blocks per side.
+int64_t default_density_block(int64_t W, int64_t H) {
+  int64_t b = 1;
+  while (ceil_div(std::max(W, H), b) > 1024) b *= 2;
+  return b;
+}
+
+// PATH with its %d (any flags and width, e.g. %06d) replaced by the generation.
+bool has_generation_field(const std::string& path) {
+  const size_t p = path.find('%');
+  if (p == std::string::npos || path.find('%', p + 1) != std::string::npos) return false;
+  size_t q = p + 1;
+  while (q < path.size() && path[q] >= '0' && path[q] <= '9') ++q;
+  return q < path.size() && path[q] == 'd';
+}
+std::string frame_path(const std::string& path, int64_t gen) {
+  const size_t p = path.find('%'), q = path.find('d', p);
+  const std::string spec = path.substr(p, q - p) + "lld";
+  char b[64];
+  std::snprintf(b, sizeof b, spec.c_str(), (long long)gen);
+  return path.substr(0, p) + b + path.substr(q + 1);
+}
+
+struct Stamp {
+  RlePattern pat;
+  int64_t x = 0, y = 0;
+};
+// The --place patterns, read and checked against the rule and the grid.
+std::vector<Stamp> load_stamps(const Options& o) {
+  std::vector<Stamp> out;
+  for (const Options::Place& pl : o.places) {
+    std::ifstream f(pl.file, std::ios::binary);
+    GOL_REQUIRE(f.good(), "--place: cannot read '" + pl.file + "'");
+    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    Stamp s;
+    try {
+      s.pat = parse_rle(text);
+    } catch (const std::exception& e) {
+      throw Error("--place " + pl.file + ": " + e.what());
+    }
+    if (!s.pat.rule.empty()) {
+      Rule r;
+      try {
+        r = parse_rule(s.pat.rule);
+      } catch (const std::exception& e) {
+        throw Error("--place " + pl.file + ": " + e.what());
+      }
+      if (r != o.rule)
+        throw Error("--place " + pl.file + ": the pattern's rule " + rule_string(r) + " is not the engine's " +
+                    rule_string(o.rule));
+    }
+    s.x = pl.centred ? (o.W - s.pat.w) / 2 : pl.x;
+    s.y = pl.centred ? (o.H - s.pat.h) / 2 : pl.y;
+    if (s.x < 0 || s.y < 0 || s.pat.w > o.W - s.x || s.pat.h > o.H - s.y)
+      throw Error("--place " + pl.file + ": rectangle x=" + std::to_string(s.x) + " y=" + std::to_string(s.y) +
+                  " w=" + std::to_string(s.pat.w) + " h=" + std::to_string(s.pat.h) + " leaves the grid of " +
+                  std::to_string(o.W) + " x " + std::to_string(o.H) + " cells (patterns do not wrap)");
+    out.push_back(std::move(s));
+  }
+  return out;
+}
+
+// A window of 0/1 cells as RLE (PATH ends in .rle) or in the text format.
+void write_window(const Options::Window& w, const std::vector<uint8_t>& cells, Rule rule) {
+  if (w.path.size() >= 4 && w.path.compare(w.path.size() - 4, 4, ".rle") == 0) {
+    std::ofstream f(w.path, std::ios::binary);
+    GOL_REQUIRE(f.good(), "--window: cannot write '" + w.path + "'");
+    f << format_rle(cells.data(), w.w, w.h, rule_string(rule));
+  } else {
+    write_text_grid(w.path, w.w, w.h, cells.data());
+  }
+}
 
 [[noreturn]] void usage(int code) {
   std::fprintf(code ? stderr : stdout,
@@ -150,6 +254,16 @@ struct Options {
                "  --checkpoint-dir DIR        ... into DIR (grid-<gen>.txt + meta.json; crash-safe)\n"
                "  --resume DIR                continue from a checkpoint: same final grid and\n"
                "                              Generations line as the uninterrupted run\n"
+               "  --place FILE[@X,Y]          stamp the RLE pattern FILE onto the loaded grid (live cells are\n"
+               "                              added), its first cell at column X, row Y, or centred;\n"
+               "                              repeatable, in order; with input 'none' the grid starts empty\n"
+               "  --density PATH              write the block populations of the final grid as a PGM image\n"
+               "  --density-block B|BYxBX     cells per block (default: the smallest power of two that gives\n"
+               "                              at most 1024 blocks per side)\n"
+               "  --density-every K           also one image per generation that is a multiple of K; PATH\n"
+               "                              must contain %%d (any width), the generation\n"
+               "  --window X,Y,W,H:PATH       write that rectangle of the final grid: RLE where PATH ends in\n"
+               "                              .rle, else the text format; repeatable\n"
                "  --show                      print the final grid with VT100 escapes\n");
   std::exit(code);
 }
@@ -214,6 +328,41 @@ Options parse(int argc, char** argv) {
       std::string v = next();
       o.graphs = v == "on" ? 1 : v == "off" ? 0 : -1;
     }
+    else if (a == "--place") {
+      const std::string v = next();
+      Options::Place pl;
+      pl.file = v;
+      const size_t at = v.rfind('@');
+      int64_t xy[2];
+      if (at != std::string::npos && parse_ints(v.substr(at + 1), 2, xy)) {
+        pl.file = v.substr(0, at);
+        pl.centred = false;
+        pl.x = xy[0], pl.y = xy[1];
+      }
+      o.places.push_back(pl);
+    } else if (a == "--density") o.density_file = next();
+    else if (a == "--density-block") {
+      const std::string v = next();
+      const size_t x = v.find('x');
+      char* rest = nullptr;
+      o.density_by = std::strtoll(v.c_str(), &rest, 10);
+      o.density_bx = o.density_by;
+      if (x != std::string::npos) {
+        if (rest != v.c_str() + x) throw Error("--density-block: B or BYxBX, got '" + v + "'");
+        o.density_bx = std::strtoll(v.c_str() + x + 1, &rest, 10);
+      }
+      if (*rest != 0 || o.density_by < 1 || o.density_bx < 1) throw Error("--density-block: B or BYxBX, got '" + v + "'");
+    } else if (a == "--density-every") {
+      o.density_every = std::atoll(next().c_str());
+      if (o.density_every < 1) throw Error("--density-every: K must be at least 1");
+    } else if (a == "--window") {
+      const std::string v = next();
+      const size_t c = v.find(':');
+      int64_t r[4];
+      if (c == std::string::npos || c + 1 >= v.size() || !parse_ints(v.substr(0, c), 4, r))
+        throw Error("--window: X,Y,W,H:PATH, got '" + v + "'");
+      o.windows.push_back({r[0], r[1], r[2], r[3], v.substr(c + 1)});
+    }
     else if (a == "--show") o.show = true;
     else if (a == "--phase-timing") o.phase_timing = true;
     else if (a == "--random") {
@@ -271,6 +420,22 @@ Options parse(int argc, char** argv) {
   if (o.W <= 0) o.W = 30;
   if (o.H <= 0) o.H = 30;
   if (o.gpus > 0) o.ranks = o.gpus;
+  if (o.density_every > 0) {
+    if (o.density_file.empty()) throw Error("--density-every needs --density PATH");
+    if (!has_generation_field(o.density_file))
+      throw Error("--density-every: the path '" + o.density_file + "' needs one %d (any width) for the generation");
+  } else if (!o.density_file.empty() && o.density_file.find('%') != std::string::npos && !has_generation_field(o.density_file)) {
+    throw Error("--density: the path '" + o.density_file + "' may hold one %d (the generation) and no other %");
+  }
+  if (!o.density_file.empty()) {
+    if (o.density_by == 0) o.density_by = o.density_bx = default_density_block(o.W, o.H);
+  }
+  for (const Options::Window& w : o.windows)
+    if (w.w < 1 || w.h < 1 || w.x < 0 || w.y < 0 || w.w > o.W - w.x || w.h > o.H - w.y ||
+        w.w > Backend::kWindowCellsMax / w.h)
+      throw Error("--window: rectangle x=" + std::to_string(w.x) + " y=" + std::to_string(w.y) + " w=" +
+                  std::to_string(w.w) + " h=" + std::to_string(w.h) + " must lie inside the grid of " +
+                  std::to_string(o.W) + " x " + std::to_string(o.H) + " cells and hold at most 2^26 cells");
   // --metrics-json does not imply --phase-timing: the event pairs around
   // every kernel, exchange, fill and reduction would sit inside the timed
   // loop that loop_ms and cell_updates_per_s report.
@@ -298,6 +463,8 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 int run(const Options& o) {
+  // Input 'none' with patterns to place: the grid starts empty.
+  const bool empty_start = o.input == "none" && !o.random && !o.places.empty() && o.resume.empty();
   const bool have_input = o.random || !o.input.empty();
   if (!have_input) {
     std::printf("Finished\n");
@@ -318,6 +485,15 @@ int run(const Options& o) {
     throw Error("--engine ref is the plain serial loop from generation 0: no checkpoint / resume");
   if (o.cycle > 0 && (engine == "ref" || o.checkpoint_every > 0))
     throw Error("--cycle runs Engine::find_cycle: not with --engine ref (the plain serial loop) or --checkpoint-every");
+  if (o.density_every > 0 && (engine == "ref" || o.cycle > 0))
+    throw Error("--density-every runs the engine in chunks: not with --engine ref (the plain serial loop) or --cycle");
+  const std::vector<Stamp> stamps = load_stamps(o);
+  double density_ms = 0;
+  int64_t density_frames = 0;
+  // The final density image's name: the reported generation where the path has a %d.
+  const auto density_path = [&](int64_t gen) {
+    return has_generation_field(o.density_file) ? frame_path(o.density_file, gen) : o.density_file;
+  };
   CycleResult cyc;
   if (engine == "ref") {
     // Exact serial semantics (src/game.c), every generation evaluated eagerly.
@@ -328,9 +504,15 @@ int run(const Options& o) {
       uint32_t th = density_thresh(o.density);
       for (int64_t r = 0; r < o.H; ++r)
         for (int64_t x = 0; x < o.W; ++x) grid[size_t(r * o.W + x)] = rng_cell(o.seed, r, x, th);
+    } else if (empty_start) {
+      grid.assign(size_t(o.W * o.H), 0);
     } else {
       read_text_grid(o.input, o.W, o.H, grid);
     }
+    for (const Stamp& s : stamps)  // stamped on the host grid before the serial loop
+      for (int64_t i = 0; i < s.pat.h; ++i)
+        for (int64_t j = 0; j < s.pat.w; ++j)
+          grid[size_t((s.y + i) * o.W + s.x + j)] |= s.pat.cells[size_t(i * s.pat.w + j)];
     read_ms = ms_since(t0);
     RefResult rr = cpu_reference_run(grid, o.W, o.H, o.gens, o.similarity, o.sim_freq, o.threads, o.rule,
                                      o.boundary, o.census_on, o.fprint_on);
@@ -344,6 +526,22 @@ int run(const Options& o) {
       auto t1 = std::chrono::steady_clock::now();
       write_text_grid(o.output, o.W, o.H, final_grid.data());
       write_ms = ms_since(t1);
+    }
+    if (!o.density_file.empty()) {
+      const int64_t nbx = ceil_div(o.W, o.density_bx), nby = ceil_div(o.H, o.density_by);
+      std::vector<uint64_t> counts(size_t(nbx * nby), 0);
+      for (int64_t r = 0; r < o.H; ++r)
+        for (int64_t x = 0; x < o.W; ++x)
+          counts[size_t((r / o.density_by) * nbx + x / o.density_bx)] += final_grid[size_t(r * o.W + x)] != 0;
+      write_pgm(density_path(res.generations), density_image(counts.data(), o.density_by, o.density_bx, o.H, o.W).data(),
+                nbx, nby);
+    }
+    for (const Options::Window& w : o.windows) {
+      std::vector<uint8_t> cells(size_t(w.w * w.h));
+      for (int64_t i = 0; i < w.h; ++i)
+        for (int64_t j = 0; j < w.w; ++j)
+          cells[size_t(i * w.w + j)] = final_grid[size_t((w.y + i) * o.W + w.x + j)] != 0;
+      write_window(w, cells, o.rule);
     }
   } else {
     const int P = std::max(1, o.ranks);
@@ -439,6 +637,8 @@ int run(const Options& o) {
       Engine& e = *engines[r];
       if (o.random) {
         e.init_random(o.seed, o.density);
+      } else if (empty_start) {
+        e.init_random(0, 0.0);  // no cell alive
       } else {
         // Uninitialised host tile (a multi-GB zero fill would cost more than
         // the parallel read that overwrites it).
@@ -450,6 +650,7 @@ int run(const Options& o) {
         e.load_cells(tile.get(), e.cols().size());
         load_ms[r] = ms_since(b);
       }
+      for (const Stamp& s : stamps) e.place(s.x, s.y, s.pat.w, s.pat.h, s.pat.cells.data(), Backend::kPlaceOr);
     });
     read_ms = ms_since(t0);
     const double read_parse_ms = *std::max_element(parse_ms.begin(), parse_ms.end());
@@ -460,6 +661,16 @@ int run(const Options& o) {
     RunResult total;
     const int64_t limit = o.gens;
     int64_t checkpoints_written = 0;
+    // One density image of the current grid (every rank takes part; rank 0's copy is written).
+    const auto write_density = [&](int64_t gen) {
+      std::vector<std::vector<uint64_t>> maps(P);
+      const auto a = std::chrono::steady_clock::now();
+      par([&](int r) { maps[r] = engines[r]->density(o.density_bx, o.density_by); });
+      density_ms = ms_since(a);
+      ++density_frames;
+      write_pgm(density_path(gen), density_image(maps[0].data(), o.density_by, o.density_bx, o.H, o.W).data(),
+                ceil_div(o.W, o.density_bx), ceil_div(o.H, o.density_by));
+    };
     if (o.cycle > 0) {
       // --cycle: Engine::find_cycle instead of the run loop; every rank takes
       // the same decisions and returns the same result.
@@ -474,9 +685,14 @@ int run(const Options& o) {
       total.extinct = cyc.stop_reason == "extinction";
       total.fingerprint = cyc.fingerprint;
     }
+    // With --checkpoint-every and --density-every a chunk ends at the next
+    // checkpoint or the next multiple of K, whichever comes first.
+    int64_t next_checkpoint = o.checkpoint_every > 0 ? engines[0]->generation() + o.checkpoint_every : -1;
     for (; o.cycle == 0;) {
       const int64_t gen = engines[0]->generation();
-      const int64_t target = o.checkpoint_every > 0 ? std::min(limit, gen + o.checkpoint_every) : limit;
+      int64_t target = limit;
+      if (next_checkpoint >= 0) target = std::min(target, next_checkpoint);
+      if (o.density_every > 0) target = std::min(target, (gen / o.density_every + 1) * o.density_every);
       par([&](int r) { results[r] = engines[r]->run_until(target); });
       double ms = 0;
       for (auto& rr : results) ms = std::max(ms, rr.loop_ms);
@@ -507,7 +723,11 @@ int run(const Options& o) {
                                                  o.similarity, o.sim_freq, o.sim_phase, &total.stop_reason);
         break;
       }
-      if (!o.checkpoint_dir.empty()) {
+      if (o.density_every > 0 && engines[0]->generation() % o.density_every == 0)
+        write_density(engines[0]->generation());
+      const bool checkpoint_due = engines[0]->generation() == next_checkpoint;
+      if (checkpoint_due) next_checkpoint += o.checkpoint_every;
+      if (checkpoint_due && !o.checkpoint_dir.empty()) {
         const int64_t g = engines[0]->generation();
         const std::string grid_path = checkpoint_begin(o.checkpoint_dir, o.W, o.H, g);
         par([&](int r) {
@@ -538,6 +758,12 @@ int run(const Options& o) {
       }
     }
     res = total;
+    if (!o.density_file.empty()) write_density(res.generations);
+    for (const Options::Window& w : o.windows) {
+      std::vector<std::vector<uint8_t>> cells(P, std::vector<uint8_t>(size_t(w.w * w.h)));
+      par([&](int r) { engines[r]->store_window(w.x, w.y, w.w, w.h, cells[r].data(), false); });
+      write_window(w, cells[0], o.rule);
+    }
 
     std::vector<double> store_ms(P, 0.0), format_ms(P, 0.0);
     if (want_grid) {
@@ -591,6 +817,9 @@ int run(const Options& o) {
         << ", \"phase_timed\": " << (res.phase_timed ? "true" : "false") << ", \"compute_ms\": " << res.compute_ms
         << ", \"halo_ms\": " << res.halo_ms << ", \"fill_ms\": " << res.fill_ms
         << ", \"allreduce_ms\": " << res.allreduce_ms;
+      if (!o.density_file.empty())
+        f << ", \"density_block\": " << jstr(std::to_string(o.density_by) + "x" + std::to_string(o.density_bx))
+          << ", \"density_ms\": " << density_ms << ", \"density_frames\": " << density_frames;
       if (o.census_on) {
         f << ", \"census\": true, \"population\": [";
         for (size_t i = 0; i < res.population.size(); ++i) f << (i ? ", " : "") << res.population[i];

@@ -12,11 +12,12 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import sys
 import time
 
-from .models.life import (DEFAULT_BOUNDARY, DEFAULT_RULE, LifeConfig, Simulation, make_backend, parse_rule,
-                          parse_tune_args, reference_run)
+from .models.life import (DEFAULT_BOUNDARY, DEFAULT_RULE, LifeConfig, Simulation, density_image, make_backend,
+                          parse_rule, parse_tune_args, read_rle, reference_run, write_pgm, write_rle)
 from .utils.metrics import stdout_lines, write_json
 
 
@@ -80,6 +81,17 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint-every", type=int, default=0)
     p.add_argument("--checkpoint-dir", default=None)
     p.add_argument("--resume", default=None, help="checkpoint directory to resume from")
+    p.add_argument("--place", action="append", default=[], metavar="FILE[@X,Y]",
+                   help="stamp the RLE pattern FILE onto the loaded grid (live cells are added), its first cell at "
+                        "column X, row Y, or centred; repeatable, in order; with input 'none' the grid starts empty")
+    p.add_argument("--density", default=None, metavar="PATH",
+                   help="write the block populations of the final grid as a PGM image")
+    p.add_argument("--density-block", default=None, metavar="B|BYxBX",
+                   help="cells per block (default: the smallest power of two that gives at most 1024 blocks per side)")
+    p.add_argument("--density-every", type=int, default=0, metavar="K",
+                   help="also one image per generation that is a multiple of K; PATH must contain %%d (any width)")
+    p.add_argument("--window", action="append", default=[], metavar="X,Y,W,H:PATH",
+                   help="write that rectangle of the final grid: RLE where PATH ends in .rle, else the text format")
     a = p.parse_args(argv)
     a.sim_freq_given = a.sim_freq is not None
     if a.sim_freq is None:
@@ -114,6 +126,89 @@ def cycle_line(cyc, limit: int) -> str:
     return f"Cycle: none within {limit} generations\n"
 
 
+_FRAME = re.compile(r"%[0-9]*d")
+
+
+def has_generation_field(path: str) -> bool:
+    return path.count("%") == 1 and _FRAME.search(path) is not None
+
+
+def density_path(path: str, gen: int) -> str:
+    return _FRAME.sub(lambda m: m.group(0) % gen, path) if has_generation_field(path) else path
+
+
+def parse_view_args(a, rule: str):
+    """--place / --density* / --window, checked like bin/gol checks them:
+    (stamps [(cells, x, y)], (by, bx) or None, windows [(x, y, w, h, path)])."""
+    W, H = a.width, a.height
+    stamps = []
+    for v in a.place:
+        file, at, xy = v.rpartition("@")
+        m = re.fullmatch(r"(-?\d+),(-?\d+)", xy) if at else None
+        if m is None:
+            file = v
+        try:
+            with open(file, "r", encoding="ascii", errors="replace") as f:
+                text = f.read()
+        except OSError:
+            raise SystemExit(f"--place: cannot read '{file}'")
+        try:
+            cells, prule = read_rle(text + "\n")
+        except RuntimeError as e:
+            raise SystemExit(f"--place {file}: {e}")
+        if prule:
+            try:
+                prule = parse_rule(prule)
+            except RuntimeError as e:
+                raise SystemExit(f"--place {file}: {e}")
+            if prule != rule:
+                raise SystemExit(f"--place {file}: the pattern's rule {prule} is not the engine's {rule}")
+        h, w = cells.shape
+        x, y = (int(m.group(1)), int(m.group(2))) if m else ((W - w) // 2, (H - h) // 2)
+        if x < 0 or y < 0 or w > W - x or h > H - y:
+            raise SystemExit(f"--place {file}: rectangle x={x} y={y} w={w} h={h} leaves the grid of {W} x {H} cells "
+                             "(patterns do not wrap)")
+        stamps.append((cells, x, y))
+    block = None
+    if a.density_every < 0 or (a.density_every and a.density is None):
+        raise SystemExit("--density-every needs K >= 1 and --density PATH")
+    if a.density is not None:
+        if a.density_every and not has_generation_field(a.density):
+            raise SystemExit(f"--density-every: the path '{a.density}' needs one %d (any width) for the generation")
+        if not a.density_every and "%" in a.density and not has_generation_field(a.density):
+            raise SystemExit(f"--density: the path '{a.density}' may hold one %d (the generation) and no other %")
+        if a.density_block is None:
+            b = 1
+            while -(-max(W, H) // b) > 1024:
+                b *= 2
+            block = (b, b)
+        else:
+            m = re.fullmatch(r"(\d+)(?:x(\d+))?", a.density_block)
+            if m is None or int(m.group(1)) < 1 or int(m.group(2) or 1) < 1:
+                raise SystemExit(f"--density-block: B or BYxBX, got '{a.density_block}'")
+            block = (int(m.group(1)), int(m.group(2) or m.group(1)))
+    windows = []
+    for v in a.window:
+        m = re.fullmatch(r"(-?\d+),(-?\d+),(-?\d+),(-?\d+):(.+)", v)
+        if m is None:
+            raise SystemExit(f"--window: X,Y,W,H:PATH, got '{v}'")
+        x, y, w, h = (int(m.group(i)) for i in range(1, 5))
+        if w < 1 or h < 1 or x < 0 or y < 0 or w > W - x or h > H - y or w * h > 1 << 26:
+            raise SystemExit(f"--window: rectangle x={x} y={y} w={w} h={h} must lie inside the grid of {W} x {H} "
+                             "cells and hold at most 2^26 cells")
+        windows.append((x, y, w, h, m.group(5)))
+    return stamps, block, windows
+
+
+def write_window_file(path: str, cells, rule: str) -> None:
+    if path.endswith(".rle"):
+        write_rle(cells, path, rule)
+    else:
+        from .utils.io import write_grid  # noqa: PLC0415
+
+        write_grid(path, cells)
+
+
 def print_tuning_keys() -> None:
     from ._native import native  # noqa: PLC0415
 
@@ -144,6 +239,12 @@ def main(argv=None) -> int:
     if a.cycle is not None and (a.engine == "ref" or a.checkpoint_every > 0):
         raise SystemExit("--cycle runs Simulation.find_cycle: not with --engine ref (the plain serial loop) or "
                          "--checkpoint-every")
+    if a.density_every > 0 and (a.engine == "ref" or a.cycle is not None):
+        raise SystemExit("--density-every runs the engine in chunks: not with --engine ref (the plain serial loop) or "
+                         "--cycle")
+    stamps, block, windows = parse_view_args(a, rule)
+    # Input 'none' with patterns to place: the grid starts empty.
+    empty_start = a.input_file == "none" and a.random is None and a.resume is None and bool(stamps)
     if a.engine == "ref":
         import numpy as np  # noqa: PLC0415
 
@@ -151,7 +252,18 @@ def main(argv=None) -> int:
         from .utils.io import read_grid, write_grid  # noqa: PLC0415
 
         t0 = time.perf_counter()
-        grid = random_grid(a.width, a.height, seed, density) if a.random else read_grid(a.input_file, a.width, a.height)
+        if a.random:
+            grid = random_grid(a.width, a.height, seed, density)
+        elif empty_start:
+            grid = np.zeros((a.height, a.width), dtype=np.uint8)
+        else:
+            grid = read_grid(a.input_file, a.width, a.height)
+        if stamps:  # stamped on the host grid before the serial loop
+            grid = np.array(grid, dtype=np.uint8)
+            grid[grid == ord("1")] = 1
+            grid[grid == ord("0")] = 0
+            for cells, x, y in stamps:
+                grid[y:y + cells.shape[0], x:x + cells.shape[1]] |= cells
         read_ms = (time.perf_counter() - t0) * 1e3
         out, gens, ms, *pop = reference_run(np.asarray(grid), a.gens, not a.no_similarity, a.sim_freq,
                                             max(1, a.threads), rule=rule, boundary=boundary,
@@ -163,7 +275,20 @@ def main(argv=None) -> int:
         t1 = time.perf_counter()
         if a.output != "none":
             write_grid(a.output, out)
-        sys.stdout.write(stdout_lines(a.style, gens, ms, read_ms, (time.perf_counter() - t1) * 1e3))
+        write_ms = (time.perf_counter() - t1) * 1e3
+        if block is not None or windows:
+            final = (np.asarray(out) == 1) | (np.asarray(out) == ord("1"))
+            final = final.astype(np.uint8)
+        if block is not None:
+            by, bx = block
+            nby, nbx = -(-a.height // by), -(-a.width // bx)
+            pad = np.zeros((nby * by, nbx * bx), dtype=np.int64)
+            pad[:a.height, :a.width] = final
+            counts = pad.reshape(nby, by, nbx, bx).sum((1, 3))
+            write_pgm(density_path(a.density, gens), density_image(counts, by, bx, a.height, a.width))
+        for x, y, w, h, path in windows:
+            write_window_file(path, final[y:y + h, x:x + w], rule)
+        sys.stdout.write(stdout_lines(a.style, gens, ms, read_ms, write_ms))
         if a.show:
             from .utils.io import show_text  # noqa: PLC0415
 
@@ -218,15 +343,32 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     if a.random is not None and not a.resume:
         sim.init_random(seed, density)
+    elif empty_start:
+        sim.init_random(0, 0.0)  # no cell alive
     else:
         sim.load_text(src)
+    for cells, x, y in stamps:
+        sim.place(cells, x, y, mode="or")
     transport.barrier()
     read_ms = (time.perf_counter() - t0) * 1e3
 
-    if a.checkpoint_every > 0:
+    density_ms, density_frames = 0.0, 0
+
+    def write_density(gen: int) -> None:
+        """One density image of the current grid (every rank takes part; rank 0 writes it)."""
+        nonlocal density_ms, density_frames
+        t = time.perf_counter()
+        counts = sim.density(block)
+        density_ms = (time.perf_counter() - t) * 1e3
+        density_frames += 1
+        if rank == 0:
+            write_pgm(density_path(a.density, gen), density_image(counts, block[0], block[1], a.height, a.width))
+
+    if a.checkpoint_every > 0 or a.density_every > 0:
         from .utils.checkpoint import run_with_checkpoints  # noqa: PLC0415
 
-        rep = run_with_checkpoints(sim, a.checkpoint_every, a.checkpoint_dir, rank == 0, transport.barrier)
+        rep = run_with_checkpoints(sim, a.checkpoint_every, a.checkpoint_dir, rank == 0, transport.barrier,
+                                   frame_every=a.density_every, on_frame=write_density)
     elif a.cycle is not None:
         from .models.life import RunReport  # noqa: PLC0415
 
@@ -237,6 +379,12 @@ def main(argv=None) -> int:
     else:
         rep = sim.run()
 
+    if block is not None:
+        write_density(rep.generations)
+    for x, y, w, h, path in windows:
+        cells = sim.window(x, y, w, h)
+        if rank == 0:
+            write_window_file(path, cells, rule)
     write_ms = 0.0
     tiles = None
     if a.show:  # every rank's tile, gathered on rank 0 (the viewer prints the whole grid)
@@ -269,6 +417,9 @@ def main(argv=None) -> int:
             rec["cycle"] = cyc.as_dict() | {"max_period": a.cycle}
             sys.stdout.write(cycle_line(cyc, a.gens))
             sys.stdout.flush()
+        if block is not None:
+            rec.update({"density_block": f"{block[0]}x{block[1]}", "density_ms": density_ms,
+                        "density_frames": density_frames})
         rec.update(sim.describe())
         rec.update({"read_ms": read_ms, "write_ms": write_ms, "width": a.width, "height": a.height})
         write_json(a.metrics_json, rec)

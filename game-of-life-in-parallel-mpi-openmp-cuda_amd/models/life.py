@@ -231,6 +231,60 @@ def grid_fingerprint(grid: np.ndarray) -> int:
     return int(native().grid_fingerprint(g))
 
 
+def _block_size(block) -> tuple[int, int]:
+    """``block`` of ``Simulation.density``: an int, or ``(by, bx)``."""
+    if isinstance(block, (int, np.integer)):
+        return int(block), int(block)
+    by, bx = block
+    return int(by), int(bx)
+
+
+def read_rle(path_or_text) -> tuple[np.ndarray, str]:
+    """An RLE pattern, from a file or (a string with a newline or a ``!``) from
+    its text: ``(cells, rule)``, cells uint8 0/1 of the header's size, rule the
+    header's rule text ("" if it names none)."""
+    text = str(path_or_text)
+    if not isinstance(path_or_text, str) or ("\n" not in text and "!" not in text):
+        with open(path_or_text, "r", encoding="ascii", errors="replace") as f:
+            text = f.read()
+    cells, rule = native().parse_rle(text)
+    return cells, str(rule)
+
+
+def write_rle(cells, path, rule: str = "B3/S23") -> None:
+    """Write a 2-D array of 0/1 cells as an RLE pattern file."""
+    a = np.ascontiguousarray(cells, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("write_rle: expected a 2-D array")
+    with open(path, "w", encoding="ascii") as f:
+        f.write(native().format_rle(a, str(rule)))
+
+
+def density_image(counts, by: int, bx: int, H: int, W: int) -> np.ndarray:
+    """Grey image of a density map: a block of n cells (clipped at the grid's
+    edge) with c live ones is 0 if c == 0, else max(1, round(255 c / n)), so a
+    single live cell in a large block still shows."""
+    c = np.asarray(counts, dtype=np.int64)
+    nby, nbx = -(-int(H) // int(by)), -(-int(W) // int(bx))
+    if c.shape != (nby, nbx):
+        raise ValueError(f"density_image: counts of shape {c.shape}, expected {(nby, nbx)}")
+    rows = np.minimum((np.arange(nby) + 1) * int(by), int(H)) - np.arange(nby) * int(by)
+    cols = np.minimum((np.arange(nbx) + 1) * int(bx), int(W)) - np.arange(nbx) * int(bx)
+    n = rows[:, None] * cols[None, :]
+    img = np.where(c == 0, 0, np.maximum(1, (255 * c + n // 2) // n))
+    return img.astype(np.uint8)
+
+
+def write_pgm(path, image) -> None:
+    """Binary PGM (P5, maxval 255) of a 2-D uint8 image."""
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("write_pgm: expected a 2-D array")
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(a.tobytes())
+
+
 class Simulation:
     """One rank's view of a (possibly decomposed) Game of Life run.
 
@@ -424,6 +478,29 @@ class Simulation:
         grid): computed on the tiles and summed over ranks, so every rank of a
         distributed run calls it."""
         return int(self._eng.fingerprint())
+
+    # -- views -----------------------------------------------------------
+    # Global coordinates, no wrap; every rank of a distributed run calls them
+    # and gets the same complete result.
+    def density(self, block) -> np.ndarray:
+        """Population of every ``block`` (an int, or ``(by, bx)``) of the current
+        grid, reduced on the device: int64, shape (ceil(H/by), ceil(W/bx)),
+        blocks clipped at the grid's edge.  At most 2^24 blocks."""
+        by, bx = _block_size(block)
+        return self._eng.density(bx, by)
+
+    def window(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """The ``h`` x ``w`` cells whose first one is column ``x``, row ``y``
+        (uint8 0/1), fetched without moving the rest of the grid."""
+        return self._eng.store_window(int(x), int(y), int(w), int(h), False)
+
+    def place(self, cells, x: int, y: int, mode: str = "copy") -> None:
+        """Write the 2-D array ``cells`` (0/1) into the grid with its first cell
+        at column ``x``, row ``y``; the rest of the grid and the generation
+        number stay.  ``mode="copy"`` overwrites the rectangle, ``"or"`` adds
+        its live cells.  (An empty grid to place into: ``init_random(seed,
+        density=0)``.)"""
+        self._eng.place(np.ascontiguousarray(cells, dtype=np.uint8), int(x), int(y), str(mode))
 
     # -- running ---------------------------------------------------------
     def _report(self, r) -> RunReport:

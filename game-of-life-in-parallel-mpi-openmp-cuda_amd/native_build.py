@@ -54,7 +54,7 @@ RULE_VARIANTS = [f"{n}_{v}" for n in RULE_NAMES for v in ("bits_dpp", "bits_add"
 HIP_SRCS = ["src/backend_hip.hip", "src/transport_rccl.hip", "kernels/life_block.hip",
             *[f"kernels/life_block_{v}.hip" for v in LIFE_VARIANTS],
             *[f"kernels/life_rule_{v}.hip" for v in RULE_VARIANTS], "kernels/life_step_lds.hip",
-            "kernels/tile_ops.hip"]
+            "kernels/tile_ops.hip", "kernels/view_ops.hip"]
 BIND_SRCS = ["src/bindings.cpp"]
 CLI_MAIN = "tools/gol_main.cpp"
 GEN_MAIN = "tools/gol_gen.cpp"

@@ -83,6 +83,17 @@ class InProcessGroup:
     def find_cycle(self, max_gens: int, max_period: int = 64, chunk: int = 0) -> list:
         return self.parallel(lambda s: s.find_cycle(max_gens, max_period, chunk))
 
+    # Views: every rank calls them; each returns the whole result.
+    def density(self, block) -> list[np.ndarray]:
+        return self.parallel(lambda s: s.density(block))
+
+    def window(self, x: int, y: int, w: int, h: int) -> list[np.ndarray]:
+        return self.parallel(lambda s: s.window(x, y, w, h))
+
+    def place(self, cells, x: int, y: int, mode: str = "copy") -> None:
+        c = np.ascontiguousarray(cells, dtype=np.uint8)
+        self.parallel(lambda s: s.place(c, x, y, mode))
+
     def gather(self) -> np.ndarray:
         out = np.zeros((self.config.height, self.config.width), dtype=np.uint8)
         for s in self.sims:

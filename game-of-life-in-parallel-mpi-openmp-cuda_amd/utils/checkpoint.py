@@ -167,16 +167,24 @@ def load_checkpoint(directory: str, **overrides) -> tuple[LifeConfig, Path]:
 
 
 def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], is_root: bool = True,
-                         barrier=None) -> RunReport:
-    """Run to gen_limit, writing a checkpoint every ``every`` generations."""
+                         barrier=None, frame_every: int = 0, on_frame=None) -> RunReport:
+    """Run to gen_limit, writing a checkpoint every ``every`` generations.
+    With ``frame_every`` = K > 0, ``on_frame(generation)`` is also called (on
+    every rank) at each generation that is a multiple of K: a chunk then ends
+    at the next checkpoint or the next multiple of K, whichever comes first."""
     cfg = sim.config
     limit = cfg.gen_limit
     eng = sim.native_engine
     total_ms, executed, exch, polls, launches = 0.0, 0, 0, 0, 0
     population = []  # LifeConfig.census: the chunks' series concatenate to the whole run's
     fingerprint = []  # LifeConfig.fingerprint: likewise
+    next_checkpoint = sim.generation + every if every > 0 else -1
     while True:
-        target = min(limit, sim.generation + every) if every > 0 else limit
+        target = limit
+        if next_checkpoint >= 0:
+            target = min(target, next_checkpoint)
+        if frame_every > 0:
+            target = min(target, (sim.generation // frame_every + 1) * frame_every)
         r = eng.run_until(target)
         total_ms += r.loop_ms
         executed += r.executed
@@ -191,5 +199,10 @@ def run_with_checkpoints(sim: Simulation, every: int, directory: Optional[str], 
             return RunReport(gens, executed, reason, total_ms, r.first_unchanged, r.extinct, exch,
                              polls, launches, cfg.width * cfg.height, population=np.concatenate(population),
                              fingerprint=np.concatenate(fingerprint))
-        if directory:
+        if frame_every > 0 and sim.generation % frame_every == 0:
+            on_frame(sim.generation)
+        due = sim.generation == next_checkpoint
+        if due:
+            next_checkpoint += every
+        if due and directory:
             save_checkpoint(sim, directory, is_root, barrier)
