@@ -105,12 +105,17 @@ __device__ __forceinline__ bool quiet_count(const LifeBlockParams& p, int item, 
 // The launch's report (one lane): `clean` and `skipped` tiles of this launch,
 // the tiles skipped by every launch so far - launches follow each other on
 // one stream, so this lane is that word's only writer - and, from a list
-// launch, the next block's candidates.
+// launch, the next block's candidates.  `before`: quiet_total(), which
+// depends on nothing in the launch - the caller loads it together with
+// whatever else it has to load.
+__device__ __forceinline__ unsigned long long quiet_total(const LifeBlockParams& p) {
+  return __hip_atomic_load(p.quiet_count + kQuietCountStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 template <bool LIST>
-__device__ __forceinline__ void quiet_publish(const LifeBlockParams& p, unsigned long long clean,
+__device__ __forceinline__ void quiet_publish(const LifeBlockParams& p, unsigned long long before, unsigned long long clean,
                                               unsigned long long skipped, unsigned long long next_items) {
   unsigned long long* const call = p.quiet_count + kQuietCountStride;
-  const unsigned long long all = __hip_atomic_load(call, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + skipped;
+  const unsigned long long all = before + skipped;
   __hip_atomic_store(call, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned long long seq = (unsigned long long)(p.quiet_seq & 0xFFFFFFu) << 40;
   __hip_atomic_store(p.quiet_report + 1, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -124,14 +129,30 @@ __device__ __forceinline__ void quiet_publish(const LifeBlockParams& p, unsigned
 // ends and are reset; changed[L] is set where some tile's current word flags
 // level L (the flag counts: exact, launched or not); the other flag-count set
 // and the next launch's ticket are zeroed.  Everything another group handed
-// over is read with 64-bit agent-scope atomics, as it was written.
+// over is read with 64-bit agent-scope atomics, as it was written, and every
+// load of this wave is issued before the first is used: the append count, the
+// flag counts, the running total of quiet_publish and the column kernel's
+// totals cost one round trip, not one after the other.
 // COLS (the column kernel): its totals reach the host as well.
 template <int T, bool COLS = false>
 __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigned long long tot, int n_items, int lane) {
   using LW = QuietListWords;
   unsigned long long* const cnt = p.quiet_lc + LW::kAppend + lane * kQuietCountStride;
-  uint32_t c = uint32_t(min(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                            (unsigned long long)p.quiet_cap));  // appends past the capacity were dropped (never: one per tile)
+  unsigned long long* const f = p.quiet_lc + LW::kFlags + p.quiet_fset * LW::kFlagSet + lane * kQuietCountStride;
+  unsigned long long* const fo = p.quiet_lc + LW::kFlags + (p.quiet_fset ^ 1) * LW::kFlagSet + lane * kQuietCountStride;
+  const unsigned long long appended = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  unsigned long long fc[quiet::flag_words(T)];
+#pragma unroll
+  for (int w = 0; w < quiet::flag_words(T); ++w) fc[w] = __hip_atomic_load(f + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long before = quiet_total(p);
+  unsigned long long col_tot[2] = {0ull, 0ull};
+  if constexpr (COLS) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      col_tot[i] = __hip_atomic_load(p.quiet_count + kQuietCountStride * (kQuietColsComputed + i), __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+  }
+  uint32_t c = uint32_t(min(appended, (unsigned long long)p.quiet_cap));  // appends past the capacity were dropped (never: one per tile)
   __hip_atomic_store(cnt, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -140,12 +161,10 @@ __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigne
   }
   p.quiet_items_next[lane] = c;
   const uint32_t n_next = __builtin_amdgcn_readlane(c, 63);
-  unsigned long long* const f = p.quiet_lc + LW::kFlags + p.quiet_fset * LW::kFlagSet + lane * kQuietCountStride;
-  unsigned long long* const fo = p.quiet_lc + LW::kFlags + (p.quiet_fset ^ 1) * LW::kFlagSet + lane * kQuietCountStride;
   uint32_t levels = 0;
 #pragma unroll
   for (int w = 0; w < quiet::flag_words(T); ++w) {
-    levels |= quiet::flag_levels(__hip_atomic_load(f + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), w);
+    levels |= quiet::flag_levels(fc[w], w);
     __hip_atomic_store(fo + w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   uint32_t any = 0;
@@ -158,14 +177,10 @@ __device__ __forceinline__ void quiet_complete(const LifeBlockParams& p, unsigne
     const unsigned long long rest = (unsigned long long)(p.ncolw * p.nseg - n_items);
     if constexpr (COLS) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
-        __hip_atomic_store(p.quiet_report + 3 + i,
-                           __hip_atomic_load(p.quiet_count + kQuietCountStride * (kQuietColsComputed + i), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      for (int i = 0; i < 2; ++i) __hip_atomic_store(p.quiet_report + 3 + i, col_tot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     // A launch with nothing to follow appended nothing: the next block runs every tile.
-    quiet_publish<true>(p, ((tot >> 20) & 0xFFFFFull) + rest, (tot >> 40) + rest,
+    quiet_publish<true>(p, before, ((tot >> 20) & 0xFFFFFull) + rest, (tot >> 40) + rest,
                         p.quiet_prev ? n_next : uint32_t(p.ncolw * p.nseg));
   }
 }
@@ -273,7 +288,7 @@ __device__ __forceinline__ void quiet_tile(const LifeBlockParams& p, const int b
     } else {
       unsigned long long tot = 0;
       if (lane == 0 && quiet_count(p, item, n_items, clean, skipped, tot))
-        quiet_publish<false>(p, (tot >> 20) & 0xFFFFFull, tot >> 40, 0ull);
+        quiet_publish<false>(p, quiet_total(p), (tot >> 20) & 0xFFFFFull, tot >> 40, 0ull);
     }
   };
 
