@@ -15,6 +15,7 @@
 #include <tuple>
 
 #include "gol/backend.hpp"
+#include "gol/batch.hpp"
 #include "gol/cpu_ref.hpp"
 #include "gol/decomp.hpp"
 #include "gol/engine.hpp"
@@ -644,6 +645,66 @@ PYBIND11_MODULE(_gol, m) {
       for (int64_t x = 0; x < W; ++x) v[size_t(r * W + x)] = uint8_t(rng_cell(seed, r, x, th));
     return to_array(std::move(v), H, W);
   }, py::arg("W"), py::arg("H"), py::arg("seed") = 1, py::arg("density") = 0.5);
+
+  // ---- batched small universes (gol/batch.hpp) ----
+  // grids: a (B, H, W) uint8 array of 0/1, or None with batch / shape / seed /
+  // density (universe b is random_grid(W, H, seed + b, density)).  Returns
+  // (generations, period, stop, population, grids or None, kernel_ms, variant).
+  m.attr("BATCH_STOP") = py::make_tuple(kBatchStopNames[0], kBatchStopNames[1], kBatchStopNames[2]);
+  m.def("simulate_batch",
+        [](std::optional<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> grids, int64_t batch,
+           int W, int H, uint64_t seed, double density, int64_t max_gens, int64_t max_period,
+           const std::string& rule, const std::string& boundary, const std::string& engine, bool return_grids,
+           int threads, int device, std::optional<Tuning> tune) -> py::tuple {
+          BatchConfig cfg;
+          BatchInput in;
+          if (grids) {
+            GOL_REQUIRE(grids->ndim() == 3, "batch: the grids are a (B, H, W) uint8 array, got " +
+                                                std::to_string(grids->ndim()) + " dimensions");
+            in.B = grids->shape(0);
+            H = int(grids->shape(1));
+            W = int(grids->shape(2));
+            in.cells = grids->data();
+          } else {
+            in.B = batch;
+            in.seed = seed;
+            in.density = density;
+          }
+          cfg.W = W;
+          cfg.H = H;
+          cfg.rule = parse_rule(rule);
+          cfg.boundary = parse_boundary(boundary);
+          cfg.max_gens = max_gens;
+          cfg.max_period = max_period;
+          cfg.want_grids = return_grids;
+          GOL_REQUIRE(engine == "cpu" || engine == "hip", "batch: engine '" + engine + "': cpu or hip");
+          BatchResult r;
+          {
+            py::gil_scoped_release rel;
+            r = engine == "hip" ? run_batch_hip(device, cfg, in, tune ? *tune : Tuning::from_env())
+                                : run_batch_cpu(threads, cfg, in);
+          }
+          const py::ssize_t B = py::ssize_t(in.B);
+          py::array_t<int32_t> gens(B), per(B), pop(B);
+          py::array_t<uint8_t> stop(B);
+          std::copy(r.generations.begin(), r.generations.end(), gens.mutable_data());
+          std::copy(r.period.begin(), r.period.end(), per.mutable_data());
+          std::copy(r.population.begin(), r.population.end(), pop.mutable_data());
+          std::copy(r.stop.begin(), r.stop.end(), stop.mutable_data());
+          py::object cells = py::none();
+          if (return_grids) {
+            auto* heap = new std::vector<uint8_t>(std::move(r.grids));
+            py::capsule owner(heap, [](void* p) { delete static_cast<std::vector<uint8_t>*>(p); });
+            cells = py::array_t<uint8_t>({int64_t(B), int64_t(H), int64_t(W)},
+                                         {int64_t(H) * W, int64_t(W), int64_t(1)}, heap->data(), owner);
+          }
+          return py::make_tuple(gens, per, stop, pop, cells, r.kernel_ms, r.variant);
+        },
+        py::arg("grids") = py::none(), py::arg("batch") = 0, py::arg("W") = 64, py::arg("H") = 64,
+        py::arg("seed") = 1, py::arg("density") = 0.5, py::arg("max_gens") = 1024, py::arg("max_period") = 64,
+        py::arg("rule") = "B3/S23", py::arg("boundary") = "torus", py::arg("engine") = "cpu",
+        py::arg("return_grids") = false, py::arg("threads") = 0, py::arg("device") = 0,
+        py::arg("tune") = py::none());
 
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",

@@ -93,6 +93,9 @@ const std::vector<TuningKey>& tuning_keys() {
        "(per GPU of the node), 0 leave placement alone"},
       {"cu_partition", "GOL_CU_PARTITION", "", 's', "tune",
        "k/n: this process's streams run on the k-th of n CU slices (ranks sharing a GPU)"},
+      {"batch_vmove", "GOL_BATCH_VMOVE", "auto", 's', "tune",
+       "vertical move of the batched-universe kernel (life_batch.hip): auto (DPP rotates at heights 64 and 16, "
+       "ds_bpermute at 8 and 32) | dpp | bpermute (every height)"},
       // --- diag ------------------------------------------------------------
       {"check_device", "GOL_CHECK_DEVICE", "0", 'i', "diag", "assert device affinity of every call and buffer"},
       {"tune_log", "GOL_TUNE_LOG", "0", 'i', "diag", "log per-launch-shape autotuning decisions"},

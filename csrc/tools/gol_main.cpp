@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "gol/backend.hpp"
+#include "gol/batch.hpp"
 #include "gol/checkpoint.hpp"
 #include "gol/cpu_ref.hpp"
 #include "gol/engine.hpp"
@@ -111,6 +112,12 @@ struct Options {
   std::string density_file;     // --density PATH ("": off)
   int64_t density_by = 0, density_bx = 0;  // --density-block (0: default_density_block)
   int64_t density_every = 0;    // --density-every K (0: the final grid only)
+  // Batched small universes (gol/batch.hpp): --batch N soups of W x H cells,
+  // seeds SEED, SEED + 1, ..., each run until it repeats or reaches --gens.
+  int64_t batch = 0;            // --batch N (0: off)
+  int64_t max_period = 64;      // --max-period P
+  std::string batch_csv;        // --batch-csv PATH
+  std::string refused_with_batch;  // the first single-universe option given, if any
 };
 
 // "a,b,c" as integers; false unless exactly n of them.
@@ -264,7 +271,15 @@ void write_window(const Options::Window& w, const std::vector<uint8_t>& cells, R
                "                              must contain %%d (any width), the generation\n"
                "  --window X,Y,W,H:PATH       write that rectangle of the final grid: RLE where PATH ends in\n"
                "                              .rle, else the text format; repeatable\n"
-               "  --show                      print the final grid with VT100 escapes\n");
+               "  --show                      print the final grid with VT100 escapes\n"
+               "  --batch N                   run N independent random universes of width x height cells (width\n"
+               "                              32 or 64, height 8, 16, 32 or 64; input 'none', --random SEED[:D]:\n"
+               "                              universe b has seed SEED + b) until each repeats or reaches --gens;\n"
+               "                              engines hip (B3/S23 and the named rules) and cpu; prints one summary\n"
+               "                              line; not with the single-universe outputs and options\n"
+               "  --max-period P              --batch: the largest period recognised, 1 to 65536 (default 64)\n"
+               "  --batch-csv PATH            --batch: write 'universe,seed,generations,stop,period,population'\n"
+               "                              lines, one per universe (stop: limit, cycle or extinction)\n");
   std::exit(code);
 }
 
@@ -277,7 +292,20 @@ Options parse(int argc, char** argv) {
       if (i + 1 >= argc) usage(2);
       return argv[++i];
     };
+    // The options of one universe's run, which --batch refuses.
+    static const char* kSingle[] = {"--output", "--census", "--fingerprint", "--cycle", "--density", "--density-block",
+                                    "--density-every", "--window", "--place", "--checkpoint-every", "--checkpoint-dir",
+                                    "--resume", "--decomp", "--show"};
+    if (o.refused_with_batch.empty() && std::find_if(std::begin(kSingle), std::end(kSingle), [&](const char* k) {
+          return a == k;
+        }) != std::end(kSingle))
+      o.refused_with_batch = a;
     if (a == "-h" || a == "--help") usage(0);
+    else if (a == "--batch") {
+      o.batch = std::atoll(next().c_str());
+      if (o.batch < 1) throw Error("--batch: the number of universes must be at least 1");
+    } else if (a == "--max-period") o.max_period = std::atoll(next().c_str());
+    else if (a == "--batch-csv") o.batch_csv = next();
     else if (a == "--engine") o.engine = next();
     else if (a == "--layout") o.layout = next();
     else if (a == "--u8-compute") {
@@ -379,6 +407,16 @@ Options parse(int argc, char** argv) {
   if (pos.size() > 0) o.W = std::atoll(pos[0].c_str());
   if (pos.size() > 1) o.H = std::atoll(pos[1].c_str());
   if (pos.size() > 2) o.input = pos[2];
+  if (o.batch > 0) {
+    if (o.input != "none" || !o.random)
+      throw Error("--batch runs random soups: give the input 'none' and --random SEED[:DENSITY]");
+    if (!o.refused_with_batch.empty())
+      throw Error("--batch with " + o.refused_with_batch + ": a batch has no single grid to write, count, view or "
+                  "checkpoint (its results go to --batch-csv and --metrics-json)");
+    if (o.gpus > 1 || o.ranks > 1) throw Error("--batch runs on one device: not with --gpus or --ranks above 1");
+    return o;
+  }
+  if (o.max_period != 64 || !o.batch_csv.empty()) throw Error("--max-period and --batch-csv need --batch N");
   if (!o.resume.empty()) {
     // The checkpoint fixes the grid and the counters; --gens / --sim-freq /
     // --no-similarity given on the command line still win.
@@ -462,7 +500,55 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// --batch: one call of the batch engine, the CSV, the metrics and one summary line.
+int run_batch(const Options& o) {
+  std::string engine = o.engine;
+  if (engine == "auto") engine = hip_available() ? "hip" : "cpu";
+  if (engine != "hip" && engine != "cpu") throw Error("--batch runs on --engine hip or cpu, not " + engine);
+  BatchConfig cfg;
+  cfg.W = int(std::min<int64_t>(o.W, 1 << 20));
+  cfg.H = int(std::min<int64_t>(o.H, 1 << 20));
+  cfg.rule = o.rule;
+  cfg.boundary = o.boundary;
+  cfg.max_gens = o.gens;
+  cfg.max_period = o.max_period;
+  BatchInput in;
+  in.B = o.batch;
+  in.seed = o.seed;
+  in.density = o.density;
+  const BatchResult r = engine == "hip" ? run_batch_hip(0, cfg, in, o.tune) : run_batch_cpu(o.threads, cfg, in);
+  int64_t counts[3] = {0, 0, 0};
+  int32_t longest = 0;
+  for (int64_t b = 0; b < in.B; ++b) {
+    ++counts[r.stop[size_t(b)]];
+    longest = std::max(longest, r.generations[size_t(b)]);
+  }
+  if (!o.batch_csv.empty()) {
+    std::ofstream f(o.batch_csv);
+    GOL_REQUIRE(f.good(), "--batch-csv: cannot write '" + o.batch_csv + "'");
+    f << "universe,seed,generations,stop,period,population\n";
+    for (int64_t b = 0; b < in.B; ++b)
+      f << b << "," << in.seed + uint64_t(b) << "," << r.generations[size_t(b)] << ","
+        << kBatchStopNames[r.stop[size_t(b)]] << "," << r.period[size_t(b)] << "," << r.population[size_t(b)] << "\n";
+  }
+  if (!o.metrics.empty()) {
+    std::ofstream f(o.metrics);
+    f << "{\"engine\": " << jstr(engine) << ", \"rule\": " << jstr(rule_string(o.rule))
+      << ", \"boundary\": " << jstr(boundary_name(o.boundary)) << ", \"W\": " << o.W << ", \"H\": " << o.H
+      << ", \"batch\": " << in.B << ", \"seed\": " << in.seed << ", \"density\": " << in.density
+      << ", \"max_gens\": " << cfg.max_gens << ", \"max_period\": " << cfg.max_period
+      << ", \"batch_kernel_ms\": " << r.kernel_ms << ", \"batch_variant\": " << jstr(r.variant)
+      << ", \"limit\": " << counts[0] << ", \"cycle\": " << counts[1] << ", \"extinction\": " << counts[2]
+      << ", \"max_generations\": " << longest << "}\n";
+  }
+  std::printf("Batch: %lld universes: %lld limit, %lld cycle, %lld extinction; largest generations %d\n",
+              (long long)in.B, (long long)counts[0], (long long)counts[1], (long long)counts[2], int(longest));
+  std::fflush(stdout);
+  return 0;
+}
+
 int run(const Options& o) {
+  if (o.batch > 0) return run_batch(o);
   // Input 'none' with patterns to place: the grid starts empty.
   const bool empty_start = o.input == "none" && !o.random && !o.places.empty() && o.resume.empty();
   const bool have_input = o.random || !o.input.empty();

@@ -11,6 +11,7 @@
 // Every configuration runs P ranks as threads (ThreadHub/ThreadTransport),
 // each with its own CPU backend, and compares the gathered grid and the
 // "Generations" value with cpu_reference_run.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -21,6 +22,7 @@
 #include <unistd.h>
 
 #include "gol/backend.hpp"
+#include "gol/batch.hpp"
 #include "gol/cpu_ref.hpp"
 #include "gol/decomp.hpp"
 #include "gol/engine.hpp"
@@ -195,6 +197,71 @@ bool text_roundtrip() {
   return ok;
 }
 
+// The CPU batch engine (gol/batch.hpp) on a handful of 32 x 8 universes, on
+// both boundaries, against a per-cell loop with the same snapshot schedule.
+bool batch_case() {
+  const int W = 32, H = 8;
+  const int64_t B = 6, max_gens = 200, P = 4;
+  bool ok = true;
+  for (const Boundary bd : {Boundary::Torus, Boundary::Dead}) {
+    std::vector<uint8_t> cells;
+    for (int64_t b = 0; b < B; ++b) {
+      const std::vector<uint8_t> g = random_cells(W, H, uint64_t(20 + b), 0.35);
+      cells.insert(cells.end(), g.begin(), g.end());
+    }
+    BatchConfig cfg;
+    cfg.W = W;
+    cfg.H = H;
+    cfg.boundary = bd;
+    cfg.max_gens = max_gens;
+    cfg.max_period = P;
+    cfg.want_grids = true;
+    BatchInput in;
+    in.B = B;
+    in.cells = cells.data();
+    const BatchResult r = run_batch_cpu(3, cfg, in);
+    for (int64_t b = 0; b < B; ++b) {
+      std::vector<uint8_t> g(cells.begin() + b * W * H, cells.begin() + (b + 1) * W * H), snap = g, nxt(g.size());
+      int32_t gens = int32_t(max_gens), period = 0;
+      int64_t s = 0;
+      for (int64_t t = 1; t <= max_gens; ++t) {
+        for (int y = 0; y < H; ++y)
+          for (int x = 0; x < W; ++x) {
+            int n = 0;
+            for (int dy = -1; dy <= 1; ++dy)
+              for (int dx = -1; dx <= 1; ++dx) {
+                if (dy == 0 && dx == 0) continue;
+                int yy = y + dy, xx = x + dx;
+                if (bd == Boundary::Torus) yy = (yy + H) % H, xx = (xx + W) % W;
+                else if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+                n += g[size_t(yy * W + xx)];
+              }
+            nxt[size_t(y * W + x)] = uint8_t(n == 3 || (n == 2 && g[size_t(y * W + x)]));
+          }
+        g = nxt;
+        if (g == snap) {
+          gens = int32_t(t), period = int32_t(t - s);
+          break;
+        }
+        if (t - s == P) snap = g, s = t;
+      }
+      int32_t pop = 0;
+      for (const uint8_t v : g) pop += v;
+      const uint8_t stop = period == 0 ? kBatchLimit : pop == 0 ? kBatchExtinction : kBatchCycle;
+      const bool same = r.generations[size_t(b)] == gens && r.period[size_t(b)] == period &&
+                        r.stop[size_t(b)] == stop && r.population[size_t(b)] == pop &&
+                        std::equal(g.begin(), g.end(), r.grids.begin() + b * W * H);
+      if (!same)
+        std::printf("  batch universe %lld (%s): got %d/%d/%s, want %d/%d/%s\n", (long long)b, boundary_name(bd),
+                    r.generations[size_t(b)], r.period[size_t(b)], kBatchStopNames[r.stop[size_t(b)]], gens, period,
+                    kBatchStopNames[stop]);
+      ok = ok && same;
+    }
+  }
+  std::printf("batch cpu 32x8, 6 universes, torus and dead -> %s\n", ok ? "ok" : "MISMATCH");
+  return ok;
+}
+
 // T0 unit checks: decomposition math and text-format edge cases.
 bool unit_checks() {
   bool ok = true;
@@ -278,6 +345,7 @@ int main() {
   ok = alloc_fault_case("u8 on bit rings", Layout::U8, 1, "1", "1x1", 1, 3) && ok;
   ok = alloc_fault_case("bits, column halos", Layout::Bits, -1, "0", "2x2", 4, 7) && ok;
   ok = text_roundtrip() && ok;
+  ok = batch_case() && ok;
   std::printf(ok ? "SELFTEST OK\n" : "SELFTEST FAILED\n");
   return ok ? 0 : 1;
 }

@@ -92,7 +92,17 @@ def parse_args(argv=None):
                    help="also one image per generation that is a multiple of K; PATH must contain %%d (any width)")
     p.add_argument("--window", action="append", default=[], metavar="X,Y,W,H:PATH",
                    help="write that rectangle of the final grid: RLE where PATH ends in .rle, else the text format")
+    p.add_argument("--batch", type=int, default=None, metavar="N",
+                   help="run N independent random universes of width x height cells (width 32 or 64, height 8, 16, "
+                        "32 or 64; input 'none', --random SEED[:D]: universe b has seed SEED + b) until each repeats "
+                        "or reaches --gens; engines hip and cpu; prints one summary line; not with the "
+                        "single-universe outputs and options")
+    p.add_argument("--max-period", type=int, default=None, metavar="P",
+                   help="--batch: the largest period recognised, 1 to 65536 (default 64)")
+    p.add_argument("--batch-csv", default=None, metavar="PATH",
+                   help="--batch: write 'universe,seed,generations,stop,period,population' lines, one per universe")
     a = p.parse_args(argv)
+    a.output_given = a.output is not None
     a.sim_freq_given = a.sim_freq is not None
     if a.sim_freq is None:
         a.sim_freq = 3
@@ -216,11 +226,72 @@ def print_tuning_keys() -> None:
         print(f"{k['key']:<22} {k['class']:<13} {k['env']:<27} default {k['default'] or repr(''):<6} {k['doc']}")
 
 
+def batch_summary(n: int, counts: dict, longest: int) -> str:
+    return (f"Batch: {n} universes: {counts['limit']} limit, {counts['cycle']} cycle, "
+            f"{counts['extinction']} extinction; largest generations {longest}\n")
+
+
+def run_batch(a) -> int:
+    """--batch: one call of simulate_batch, the CSV, the metrics and one summary line."""
+    from .models.batch import simulate_batch  # noqa: PLC0415
+
+    if a.input_file != "none" or a.random is None:
+        raise SystemExit("--batch runs random soups: give the input 'none' and --random SEED[:DENSITY]")
+    single = {"--output": a.output_given, "--census": a.census is not None,
+              "--fingerprint": a.fingerprint is not None, "--cycle": a.cycle is not None,
+              "--density": a.density is not None, "--density-block": a.density_block is not None,
+              "--density-every": a.density_every != 0, "--window": bool(a.window), "--place": bool(a.place),
+              "--checkpoint-every": a.checkpoint_every != 0, "--checkpoint-dir": a.checkpoint_dir is not None,
+              "--resume": a.resume is not None, "--decomp": a.decomp != "auto", "--show": a.show}
+    for opt, given in single.items():
+        if given:
+            raise SystemExit(f"--batch with {opt}: a batch has no single grid to write, count, view or checkpoint "
+                             "(its results go to --batch-csv and --metrics-json)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--batch runs on one device: not under torchrun with more than one process")
+    if a.batch < 1:
+        raise SystemExit("--batch: the number of universes must be at least 1")
+    if a.engine == "ref":
+        raise SystemExit("--batch runs on --engine hip or cpu, not ref")
+    s, _, d = a.random.partition(":")
+    seed, density = int(s), float(d) if d else 0.5
+    try:
+        r = simulate_batch(batch=a.batch, shape=(a.width, a.height), random=(seed, density), max_gens=a.gens,
+                           max_period=64 if a.max_period is None else a.max_period,
+                           rule=a.rule if a.rule is not None else DEFAULT_RULE,
+                           boundary=a.boundary or DEFAULT_BOUNDARY, engine=a.engine, threads=a.threads,
+                           tune=parse_tune_args(a.tune))
+    except RuntimeError as e:
+        raise SystemExit(f"gol: error: {e}")
+    names = r.stop_names()
+    if a.batch_csv is not None:
+        with open(a.batch_csv, "w") as f:
+            f.write("universe,seed,generations,stop,period,population\n")
+            for b in range(a.batch):
+                f.write(f"{b},{(seed + b) % 2**64},{int(r.generations[b])},{names[b]},{int(r.period[b])},"
+                        f"{int(r.population[b])}\n")
+    counts = r.counts()
+    longest = int(r.generations.max())
+    write_json(a.metrics_json, {"engine": "cpu" if r.variant.startswith("batch cpu") else "hip", "rule": parse_rule(a.rule) if a.rule is not None else DEFAULT_RULE,
+                                "boundary": a.boundary or DEFAULT_BOUNDARY, "width": a.width, "height": a.height,
+                                "batch": a.batch, "seed": seed, "density": density, "max_gens": a.gens,
+                                "max_period": 64 if a.max_period is None else a.max_period,
+                                "batch_kernel_ms": r.kernel_ms, "batch_variant": r.variant, **counts,
+                                "max_generations": longest})
+    sys.stdout.write(batch_summary(a.batch, counts, longest))
+    sys.stdout.flush()
+    return 0
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     if "help" in a.tune:
         print_tuning_keys()
         return 0
+    if a.batch is not None:
+        return run_batch(a)
+    if a.max_period is not None or a.batch_csv is not None:
+        raise SystemExit("--max-period and --batch-csv need --batch N")
     if a.input_file is None and a.random is None and a.resume is None:
         print("Finished")
         return 0

@@ -32,7 +32,7 @@ BUILD = REPO / "build" / "obj"
 
 HOST_SRCS = ["src/decomp.cpp", "src/parallel.cpp", "src/backend_cpu.cpp", "src/transport.cpp",
              "src/engine.cpp", "src/io.cpp", "src/cpu_ref.cpp", "src/checkpoint.cpp", "src/tuning.cpp",
-             "src/numa.cpp"]
+             "src/numa.cpp", "src/batch_cpu.cpp"]
 # One translation unit per compiled kernel variant (layout x cross-lane
 # window), so the build compiles them in parallel.  The variants measured
 # slower than these (resident epochs, persistent dataflow launches, short
@@ -54,7 +54,8 @@ RULE_VARIANTS = [f"{n}_{v}" for n in RULE_NAMES for v in ("bits_dpp", "bits_add"
 HIP_SRCS = ["src/backend_hip.hip", "src/transport_rccl.hip", "kernels/life_block.hip",
             *[f"kernels/life_block_{v}.hip" for v in LIFE_VARIANTS],
             *[f"kernels/life_rule_{v}.hip" for v in RULE_VARIANTS], "kernels/life_step_lds.hip",
-            "kernels/tile_ops.hip", "kernels/view_ops.hip"]
+            "kernels/tile_ops.hip", "kernels/view_ops.hip",
+            "kernels/life_batch.hip"]  # batched small universes (gol/batch.hpp)
 BIND_SRCS = ["src/bindings.cpp"]
 CLI_MAIN = "tools/gol_main.cpp"
 GEN_MAIN = "tools/gol_gen.cpp"
