@@ -1,5 +1,6 @@
-// Batched small universes: B independent W x H grids of one rule and one
-// boundary, each advanced until it repeats or reaches max_gens.
+// Batched small universes: B independent W x H grids of one boundary and one
+// rule (or one rule per universe, BatchConfig::rules), each advanced until it
+// repeats or reaches max_gens.
 //
 // The engine (engine.hpp) streams one huge grid through temporal blocks; a
 // thousand 64 x 64 soups through it are a thousand launch-latency-bound runs.
@@ -43,6 +44,14 @@ struct BatchConfig {
   int64_t max_gens = 1024;
   int64_t max_period = 64;
   bool want_grids = false;
+  // Rule sweeps.  Empty: every universe runs `rule`.  Else R rules of K =
+  // soups_per_rule universes each, B = R * K: universe u runs rules[u / K] on
+  // soup `share_soups ? u % K : u`.  The soup index selects the cells read
+  // (with share_soups the input holds K grids, not B) and the seed, seed + soup.
+  // The hip engine then takes the rules as data (any rule without B0).
+  std::vector<Rule> rules;
+  int64_t soups_per_rule = 1;
+  bool share_soups = false;
 };
 
 // What a batch starts from: B grids of 0/1 bytes, (B, H, W) row-major, or
@@ -63,13 +72,37 @@ struct BatchResult {
 };
 
 // Refuses what no engine runs, each message naming the limit it enforces:
-// the shape, B, max_period, max_gens, B0 rules, cells other than 0/1.
+// the shape, B, max_period, max_gens, B0 rules (in `rules` with the index),
+// K < 1, R * K outside 1..2^24 or other than B, cells other than 0/1.
 void validate_batch(const BatchConfig& cfg, const BatchInput& in);
+
+// The rule and the soup index of universe u (see BatchConfig::rules).
+inline Rule batch_rule(const BatchConfig& cfg, int64_t u) {
+  return cfg.rules.empty() ? cfg.rule : cfg.rules[size_t(u / cfg.soups_per_rule)];
+}
+inline int64_t batch_soup(const BatchConfig& cfg, int64_t u) {
+  return !cfg.rules.empty() && cfg.share_soups ? u % cfg.soups_per_rule : u;
+}
+// Grids in BatchInput::cells.
+inline int64_t batch_soups(const BatchConfig& cfg, const BatchInput& in) {
+  return !cfg.rules.empty() && cfg.share_soups ? cfg.soups_per_rule : in.B;
+}
+// The Life-like rules without B0 in a fixed order (gol_amd.life_like_rules):
+// rule i has birth mask (i & 0xFF) << 1 and survive mask i >> 8.
+constexpr int64_t kLifeLikeRules = int64_t(1) << 17;
+constexpr Rule life_like_rule(int64_t i) { return Rule{uint16_t((i & 0xFF) << 1), uint16_t(i >> 8)}; }
+
+// The end of an engine's variant text: the rule, or "rule table R rules x K".
+inline std::string batch_rule_text(const BatchConfig& cfg) {
+  if (cfg.rules.empty()) return rule_string(cfg.rule);
+  return "rule table " + std::to_string(cfg.rules.size()) + " rules x " + std::to_string(cfg.soups_per_rule);
+}
 
 // threads <= 0: the global host pool.  Any rule without B0.
 BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput& in);
-// One kernel launch on `device` (life_batch.hip).  B3/S23 and the rules of
-// life_rules.def; tuning batch_vmove picks the vertical move.
+// One kernel launch on `device` (life_batch.hip).  `rule`: B3/S23 and the rules
+// of life_rules.def, compiled in; `rules`: any, read from a table on the device.
+// Tuning batch_vmove picks the vertical move.
 BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& in,
                           const Tuning& tune = Tuning::from_env());
 

@@ -26,6 +26,12 @@
 //   * The state is read once (0/1 bytes packed in the lane, or generated in
 //     the lane from the counter-based RNG, so a random soup never exists in
 //     memory) and written at most once (only when the grids are asked for).
+//   * The rule is a policy.  Compiled<R> folds one rule of life_rules.def in
+//     at compile time.  RuleWord takes the rule as data: every lane loads its
+//     universe's rule word once and expands it into 17 all-ones / all-zero
+//     registers, the entries of the truth table over (centre, 3x3 sum); a
+//     generation evaluates the table as a tree of v_bitop3 selects.  The
+//     universes of one wave may all have different rules.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -54,6 +60,11 @@ struct Args {
   int32_t* population;
   uint8_t* stop;
   uint32_t* words;       // (B, H, W/32) final words, or nullptr
+  // Rule table (RuleWord only): universe u runs rule u / K on soup
+  // share ? u % K : u; a word is birth | survive << 16.
+  const uint32_t* rules;
+  uint32_t K;
+  uint32_t share;
 };
 
 // Lane i receives v of the lane one row above (kUp) or below within its
@@ -73,6 +84,72 @@ __device__ __forceinline__ uint32_t vmove(uint32_t v, int src4) {
   }
 }
 
+// ---- rule policies ------------------------------------------------------------
+// State: what a lane keeps of its universe's rule over the loop.  soup(): the
+// index of the universe's cells and seed.  load() runs only for valid lanes.
+
+// One rule of life_block_impl.hpp, folded in at compile time.
+template <class R>
+struct Compiled {
+  struct State {};
+  __device__ static __forceinline__ int64_t soup(const Args&, int64_t u) { return u; }
+  __device__ static __forceinline__ void load(State&, const Args&, int64_t) {}
+  __device__ static __forceinline__ uint32_t eval(const State&, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1,
+                                                  uint32_t c0, uint32_t c1, uint32_t ctr) {
+    return R::eval(a0, a1, b0, b1, c0, c1, ctr);
+  }
+};
+
+// The rule as data.  With S = 0..9 the 3x3 sum including the centre (bit
+// planes s0..s3 as in common.hpp rule_host), next = ctr ? survive[S - 1] :
+// birth[S].  A live centre has S >= 1, a dead one S <= 8 and B0 is refused, so
+// the table's entry at S is E[S] = ctr ? sv[S - 1] : b[S] for S = 1..8,
+// E[0] = 0 and E[9] = sv[8]: 8 selects on ctr, then a select tree over the
+// bits of S (5 on s0, 2 on s1, 1 on s2, 1 on s3).  24 v_bitop3 / v_xor a word
+// against Conway's 8.  The entries are per-lane values at every height.
+struct RuleWord {
+  struct State {
+    uint32_t b[9] = {};   // b[n]: all ones where born at n neighbours (b[0] unused)
+    uint32_t sv[9] = {};  // sv[n]: all ones where surviving at n neighbours
+  };
+  __device__ static __forceinline__ int64_t soup(const Args& a, int64_t u) {
+    return a.share ? int64_t(uint32_t(u) % a.K) : u;
+  }
+  __device__ static __forceinline__ void load(State& st, const Args& a, int64_t u) {
+    const uint32_t w = a.rules[uint32_t(u) / a.K];
+#pragma unroll
+    for (int n = 0; n < 9; ++n) {
+      st.b[n] = 0u - ((w >> n) & 1u);
+      st.sv[n] = 0u - ((w >> (16 + n)) & 1u);
+    }
+  }
+  __device__ static __forceinline__ uint32_t eval(const State& st, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1,
+                                                  uint32_t c0, uint32_t c1, uint32_t ctr) {
+    using lb::bop3;
+    const uint32_t s0 = bop3<tt::XOR3>(a0, b0, c0);
+    const uint32_t x1 = bop3<tt::MAJ>(a0, b0, c0);
+    const uint32_t y0 = bop3<tt::XOR3>(a1, b1, c1);
+    const uint32_t y1 = bop3<tt::MAJ>(a1, b1, c1);
+    const uint32_t s1 = x1 ^ y0;
+    const uint32_t s2 = bop3<tt::XOR_AND>(x1, y0, y1);
+    const uint32_t s3 = bop3<tt::AND3>(x1, y0, y1);
+    uint32_t e[10];
+    e[0] = 0u;
+#pragma unroll
+    for (int n = 1; n <= 8; ++n) e[n] = bop3<tt::SEL>(ctr, st.sv[n - 1], st.b[n]);
+    e[9] = st.sv[8];
+    const uint32_t p01 = s0 & e[1];
+    const uint32_t p23 = bop3<tt::SEL>(s0, e[3], e[2]);
+    const uint32_t p45 = bop3<tt::SEL>(s0, e[5], e[4]);
+    const uint32_t p67 = bop3<tt::SEL>(s0, e[7], e[6]);
+    const uint32_t p89 = bop3<tt::SEL>(s0, e[9], e[8]);
+    const uint32_t q03 = bop3<tt::SEL>(s1, p23, p01);
+    const uint32_t q47 = bop3<tt::SEL>(s1, p67, p45);
+    const uint32_t r07 = bop3<tt::SEL>(s2, q47, q03);
+    return bop3<tt::SEL>(s3, p89, r07);
+  }
+};
+
 template <int NW, int H, class Rule, bool DEAD, int VM>
 __global__ __launch_bounds__(kBlock) void life_batch_kernel(const Args a) {
   using lb::bop3;
@@ -88,9 +165,12 @@ __global__ __launch_bounds__(kBlock) void life_batch_kernel(const Args a) {
   uint32_t c[NW];
 #pragma unroll
   for (int i = 0; i < NW; ++i) c[i] = 0u;
+  typename Rule::State rule;
   if (valid) {
+    Rule::load(rule, a, u);
+    const int64_t soup = Rule::soup(a, u);
     if (a.cells) {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.cells + (u * H + row) * int64_t(32 * NW));
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.cells + (soup * H + row) * int64_t(32 * NW));
 #pragma unroll
       for (int i = 0; i < NW; ++i) {
         uint32_t w = 0;
@@ -102,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void life_batch_kernel(const Args a) {
         c[i] = w;
       }
     } else {
-      const uint64_t seed = a.seed + uint64_t(u);
+      const uint64_t seed = a.seed + uint64_t(soup);
 #pragma unroll
       for (int i = 0; i < NW; ++i) {
         uint32_t w = 0;
@@ -145,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void life_batch_kernel(const Args a) {
         a0 &= up_keep, a1 &= up_keep;
         d0 &= dn_keep, d1 &= dn_keep;
       }
-      nxt[i] = Rule::eval(a0, a1, h0[i], h1[i], d0, d1, c[i]);
+      nxt[i] = Rule::eval(rule, a0, a1, h0[i], h1[i], d0, d1, c[i]);
       diff |= nxt[i] ^ snap[i];
     }
     ++t, ++k;
@@ -228,11 +308,17 @@ RuleTable make_table(Rule rule) {
 
 const std::vector<RuleTable>& tables() {
   static const std::vector<RuleTable> t = {
-      make_table<lb::Conway>(Rule{}),
-#define GOL_RULE(name, B, S) make_table<lb::LifeLike<B, S>>(Rule{B, S}),
+      make_table<Compiled<lb::Conway>>(Rule{}),
+#define GOL_RULE(name, B, S) make_table<Compiled<lb::LifeLike<B, S>>>(Rule{B, S}),
 #include "life_rules.def"
 #undef GOL_RULE
   };
+  return t;
+}
+
+// The kernels that take their rules from Args::rules.
+const RuleTable& word_table() {
+  static const RuleTable t = make_table<RuleWord>(Rule{0, 0});
   return t;
 }
 
@@ -255,9 +341,10 @@ struct DeviceBuf {
 BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& in, const Tuning& tune) {
   namespace hb = hipk::batch;
   validate_batch(cfg, in);
-  const hb::RuleTable* table = nullptr;
+  const bool by_word = !cfg.rules.empty();
+  const hb::RuleTable* table = by_word ? &hb::word_table() : nullptr;
   for (const hb::RuleTable& t : hb::tables())
-    if (t.rule == cfg.rule) table = &t;
+    if (!by_word && t.rule == cfg.rule) table = &t;
   if (!table) {
     std::string have;
     for (const Rule r : hip_rules()) have += std::string(have.empty() ? "" : ", ") + rule_string(r);
@@ -279,12 +366,19 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   const hb::LaunchFn fn = table->fn[NW - 1][hi][dead ? 1 : 0][vm];
 
   DeviceScope scope(device);
-  hb::DeviceBuf<uint8_t> d_cells(in.cells ? size_t(B) * H * W : 0);
+  const size_t n_cells = in.cells ? size_t(batch_soups(cfg, in)) * H * W : 0;
+  hb::DeviceBuf<uint8_t> d_cells(n_cells);
+  hb::DeviceBuf<uint32_t> d_rules(cfg.rules.size());
   const size_t nb = size_t(B);
   hb::DeviceBuf<int32_t> d_gens(nb), d_per(nb), d_pop(nb);
   hb::DeviceBuf<uint8_t> d_stop(nb);
   hb::DeviceBuf<uint32_t> d_words(cfg.want_grids ? size_t(B) * H * NW : 0);
-  if (in.cells) HIP_CHECK(hipMemcpy(d_cells.p, in.cells, size_t(B) * H * W, hipMemcpyHostToDevice));
+  if (in.cells) HIP_CHECK(hipMemcpy(d_cells.p, in.cells, n_cells, hipMemcpyHostToDevice));
+  if (by_word) {
+    std::vector<uint32_t> words(cfg.rules.size());
+    for (size_t r = 0; r < words.size(); ++r) words[r] = uint32_t(cfg.rules[r].birth) | uint32_t(cfg.rules[r].survive) << 16;
+    HIP_CHECK(hipMemcpy(d_rules.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
 
   hb::Args a{};
   a.B = B;
@@ -298,6 +392,9 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   a.population = d_pop.p;
   a.stop = d_stop.p;
   a.words = d_words.p;
+  a.rules = d_rules.p;
+  a.K = uint32_t(by_word ? cfg.soups_per_rule : 1);
+  a.share = cfg.share_soups ? 1u : 0u;
 
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIP_CHECK(hipEventCreate(&e0));
@@ -334,7 +431,7 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   }
   const char* move = vm == hb::kVmBpermute ? "ds_bpermute" : H == 64 ? "dpp wave_ror/rol" : "dpp row_ror";
   res.variant = "batch " + std::to_string(W) + "x" + std::to_string(H) + " " + boundary_name(cfg.boundary) + " " +
-                std::to_string(upw) + "/wave " + move + " " + rule_string(cfg.rule);
+                std::to_string(upw) + "/wave " + move + " " + batch_rule_text(cfg);
   return res;
 }
 

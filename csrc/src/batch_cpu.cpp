@@ -28,8 +28,22 @@ void validate_batch(const BatchConfig& cfg, const BatchInput& in) {
     fail("batch: max_gens = " + std::to_string(cfg.max_gens) + ": must be 1 to 2^24 = " +
          std::to_string(kBatchMaxGens));
   require_no_b0(cfg.rule, rule_string(cfg.rule));
+  if (!cfg.rules.empty()) {
+    const int64_t R = int64_t(cfg.rules.size()), K = cfg.soups_per_rule;
+    if (K < 1) fail("batch: " + std::to_string(K) + " soups per rule: must be at least 1");
+    if (K > kBatchMax || R * K > kBatchMax)
+      fail("batch: " + std::to_string(R) + " rules x " + std::to_string(K) + " soups: a batch holds 1 to 2^24 = " +
+           std::to_string(kBatchMax) + " universes");
+    if (in.B != R * K)
+      fail("batch: " + std::to_string(in.B) + " universes, but " + std::to_string(R) + " rules x " +
+           std::to_string(K) + " soups = " + std::to_string(R * K));
+    for (int64_t r = 0; r < R; ++r)
+      if (cfg.rules[size_t(r)].birth & 1u)
+        fail("batch: rule " + std::to_string(r) + " of the list, " + rule_string(cfg.rules[size_t(r)]) +
+             ": B0 is not supported (an empty universe would not stay empty)");
+  }
   if (in.cells) {
-    const int64_t n = in.B * cfg.H * cfg.W;
+    const int64_t n = batch_soups(cfg, in) * cfg.H * cfg.W;
     for (int64_t i = 0; i < n; ++i)
       if (in.cells[i] > 1)
         fail("batch: cell " + std::to_string(i % cfg.W) + " of row " + std::to_string(i / cfg.W % cfg.H) +
@@ -46,7 +60,7 @@ struct HSum64 {
 
 // One universe from its start to its stop; rows[] ends as the final grid.
 template <bool kConway>
-void run_universe(const BatchConfig& cfg, uint64_t* rows, int32_t& generations, int32_t& period) {
+void run_universe(const BatchConfig& cfg, Rule rule, uint64_t* rows, int32_t& generations, int32_t& period) {
   const int W = cfg.W, H = cfg.H;
   const uint64_t mask = W == 64 ? ~uint64_t(0) : (uint64_t(1) << W) - 1;
   const bool torus = cfg.boundary == Boundary::Torus;
@@ -73,7 +87,7 @@ void run_universe(const BatchConfig& cfg, uint64_t* rows, int32_t& generations, 
         const HSum ha{uint32_t(a.h0 >> sh), uint32_t(a.h1 >> sh)}, hb{uint32_t(b.h0 >> sh), uint32_t(b.h1 >> sh)},
             hc{uint32_t(c.h0 >> sh), uint32_t(c.h1 >> sh)};
         const uint32_t ctr = uint32_t(rows[y] >> sh);
-        const uint32_t v = kConway ? rule_host(ha, hb, hc, ctr) : rule_host(cfg.rule, ha, hb, hc, ctr);
+        const uint32_t v = kConway ? rule_host(ha, hb, hc, ctr) : rule_host(rule, ha, hb, hc, ctr);
         out |= uint64_t(v) << sh;
       }
       nxt[y] = out;
@@ -108,21 +122,22 @@ BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput&
   res.stop.assign(size_t(B), 0);
   if (cfg.want_grids) res.grids.assign(size_t(B * H * W), 0);
   const uint32_t th = density_thresh(in.density);
-  const bool conway = rule_is_default(cfg.rule);
   const auto body = [&](int64_t b0, int64_t b1) {
     uint64_t rows[64];
     for (int64_t b = b0; b < b1; ++b) {
+      const Rule rule = batch_rule(cfg, b);
+      const int64_t soup = batch_soup(cfg, b);
       for (int y = 0; y < H; ++y) {
         uint64_t v = 0;
         for (int x = 0; x < W; ++x) {
-          const bool live = in.cells ? in.cells[size_t((b * H + y) * W + x)] != 0
-                                     : rng_cell(in.seed + uint64_t(b), y, x, th);
+          const bool live = in.cells ? in.cells[size_t((soup * H + y) * W + x)] != 0
+                                     : rng_cell(in.seed + uint64_t(soup), y, x, th);
           v |= uint64_t(live) << x;
         }
         rows[y] = v;
       }
-      if (conway) run_universe<true>(cfg, rows, res.generations[size_t(b)], res.period[size_t(b)]);
-      else run_universe<false>(cfg, rows, res.generations[size_t(b)], res.period[size_t(b)]);
+      if (rule_is_default(rule)) run_universe<true>(cfg, rule, rows, res.generations[size_t(b)], res.period[size_t(b)]);
+      else run_universe<false>(cfg, rule, rows, res.generations[size_t(b)], res.period[size_t(b)]);
       int32_t pop = 0;
       for (int y = 0; y < H; ++y) pop += __builtin_popcountll(rows[y]);
       res.population[size_t(b)] = pop;
@@ -141,7 +156,7 @@ BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput&
   }
   res.kernel_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   res.variant = "batch cpu " + std::to_string(W) + "x" + std::to_string(H) + " " + boundary_name(cfg.boundary) +
-                " rows64 " + rule_string(cfg.rule);
+                " rows64 " + batch_rule_text(cfg);
   return res;
 }
 

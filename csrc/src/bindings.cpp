@@ -655,13 +655,25 @@ PYBIND11_MODULE(_gol, m) {
         [](std::optional<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> grids, int64_t batch,
            int W, int H, uint64_t seed, double density, int64_t max_gens, int64_t max_period,
            const std::string& rule, const std::string& boundary, const std::string& engine, bool return_grids,
-           int threads, int device, std::optional<Tuning> tune) -> py::tuple {
+           int threads, int device, std::optional<Tuning> tune, const std::vector<std::string>& rules,
+           int64_t soups, bool share_soups) -> py::tuple {
           BatchConfig cfg;
           BatchInput in;
+          for (size_t r = 0; r < rules.size(); ++r) {
+            try {
+              cfg.rules.push_back(parse_rule(rules[r]));
+            } catch (const std::exception& e) {
+              throw Error("batch: rule " + std::to_string(r) + " of the list: " + e.what());
+            }
+          }
+          cfg.soups_per_rule = soups;
+          cfg.share_soups = share_soups;
           if (grids) {
             GOL_REQUIRE(grids->ndim() == 3, "batch: the grids are a (B, H, W) uint8 array, got " +
                                                 std::to_string(grids->ndim()) + " dimensions");
             in.B = grids->shape(0);
+            // Shared soups: the K grids serve every rule (validate_batch checks K).
+            if (!cfg.rules.empty() && share_soups && in.B == soups) in.B = int64_t(cfg.rules.size()) * soups;
             H = int(grids->shape(1));
             W = int(grids->shape(2));
             in.cells = grids->data();
@@ -704,7 +716,8 @@ PYBIND11_MODULE(_gol, m) {
         py::arg("seed") = 1, py::arg("density") = 0.5, py::arg("max_gens") = 1024, py::arg("max_period") = 64,
         py::arg("rule") = "B3/S23", py::arg("boundary") = "torus", py::arg("engine") = "cpu",
         py::arg("return_grids") = false, py::arg("threads") = 0, py::arg("device") = 0,
-        py::arg("tune") = py::none());
+        py::arg("tune") = py::none(), py::arg("rules") = std::vector<std::string>{}, py::arg("soups") = 1,
+        py::arg("share_soups") = false);
 
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",

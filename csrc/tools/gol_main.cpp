@@ -117,6 +117,12 @@ struct Options {
   int64_t batch = 0;            // --batch N (0: off)
   int64_t max_period = 64;      // --max-period P
   std::string batch_csv;        // --batch-csv PATH
+  // A rule per universe: --batch-rules FILE|all, R rules.  Without --soups
+  // universe b runs rule b on the soup of seed SEED + b; with --soups K
+  // universe r*K + j runs rule r on the soup of seed SEED + j.
+  std::string batch_rules;      // --batch-rules FILE|all ("": one rule, --rule)
+  int64_t soups = 0;            // --soups K (0: not given)
+  std::string rules_csv;        // --rules-csv PATH
   std::string refused_with_batch;  // the first single-universe option given, if any
 };
 
@@ -279,7 +285,18 @@ void write_window(const Options::Window& w, const std::vector<uint8_t>& cells, R
                "                              line; not with the single-universe outputs and options\n"
                "  --max-period P              --batch: the largest period recognised, 1 to 65536 (default 64)\n"
                "  --batch-csv PATH            --batch: write 'universe,seed,generations,stop,period,population'\n"
-               "                              lines, one per universe (stop: limit, cycle or extinction)\n");
+               "                              lines, one per universe (stop: limit, cycle or extinction)\n"
+               "  --batch-rules FILE|all      --batch with a rule per universe, N = the number of rules R (an explicit\n"
+               "                              --batch N must agree): FILE holds one rule per line (# comments and\n"
+               "                              blank lines skipped), all = the 131072 Life-like rules without B0;\n"
+               "                              universe b runs rule b on seed SEED + b; any rule on either engine;\n"
+               "                              not with --rule; prints a second line 'Rules: R rules x K soups' and\n"
+               "                              adds a 'rule' column after 'seed' to --batch-csv\n"
+               "  --soups K                   --batch-rules: the cross product, N = R * K: universe r*K + j runs rule\n"
+               "                              r on seed SEED + j\n"
+               "  --rules-csv PATH            --batch-rules: write 'rule,soups,limit,cycle,extinction,\n"
+               "                              mean_generations,max_generations,max_period,mean_population' lines,\n"
+               "                              one per rule\n");
   std::exit(code);
 }
 
@@ -306,6 +323,12 @@ Options parse(int argc, char** argv) {
       if (o.batch < 1) throw Error("--batch: the number of universes must be at least 1");
     } else if (a == "--max-period") o.max_period = std::atoll(next().c_str());
     else if (a == "--batch-csv") o.batch_csv = next();
+    else if (a == "--batch-rules") o.batch_rules = next();
+    else if (a == "--rules-csv") o.rules_csv = next();
+    else if (a == "--soups") {
+      o.soups = std::atoll(next().c_str());
+      if (o.soups < 1) throw Error("--soups: the number of soups per rule must be at least 1");
+    }
     else if (a == "--engine") o.engine = next();
     else if (a == "--layout") o.layout = next();
     else if (a == "--u8-compute") {
@@ -407,7 +430,11 @@ Options parse(int argc, char** argv) {
   if (pos.size() > 0) o.W = std::atoll(pos[0].c_str());
   if (pos.size() > 1) o.H = std::atoll(pos[1].c_str());
   if (pos.size() > 2) o.input = pos[2];
-  if (o.batch > 0) {
+  if (o.batch_rules.empty() && (o.soups > 0 || !o.rules_csv.empty()))
+    throw Error("--soups and --rules-csv need --batch-rules FILE|all");
+  if (o.batch > 0 || !o.batch_rules.empty()) {
+    if (!o.batch_rules.empty() && o.rule_set)
+      throw Error("--batch-rules with --rule: the rules come from the list");
     if (o.input != "none" || !o.random)
       throw Error("--batch runs random soups: give the input 'none' and --random SEED[:DENSITY]");
     if (!o.refused_with_batch.empty())
@@ -500,7 +527,33 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// --batch: one call of the batch engine, the CSV, the metrics and one summary line.
+// --batch-rules: the rules of FILE (one per line, # comments and blank lines
+// skipped), or all Life-like rules without B0.
+std::vector<Rule> load_batch_rules(const std::string& arg) {
+  std::vector<Rule> rules;
+  if (arg == "all") {
+    for (int64_t i = 0; i < kLifeLikeRules; ++i) rules.push_back(life_like_rule(i));
+    return rules;
+  }
+  std::ifstream f(arg);
+  GOL_REQUIRE(f.good(), "--batch-rules: cannot read '" + arg + "'");
+  std::string line;
+  for (int64_t n = 1; std::getline(f, line); ++n) {
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.erase(hash);
+    const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+    if (b == std::string::npos) continue;
+    try {
+      rules.push_back(parse_rule(line.substr(b, e - b + 1)));
+    } catch (const std::exception& ex) {
+      throw Error("--batch-rules " + arg + ": line " + std::to_string(n) + ": " + ex.what());
+    }
+  }
+  if (rules.empty()) throw Error("--batch-rules " + arg + ": the file names no rule");
+  return rules;
+}
+
+// --batch: one call of the batch engine, the CSVs, the metrics and the summary.
 int run_batch(const Options& o) {
   std::string engine = o.engine;
   if (engine == "auto") engine = hip_available() ? "hip" : "cpu";
@@ -514,6 +567,18 @@ int run_batch(const Options& o) {
   cfg.max_period = o.max_period;
   BatchInput in;
   in.B = o.batch;
+  const bool by_rule = !o.batch_rules.empty();
+  const int64_t K = std::max<int64_t>(o.soups, 1);
+  if (by_rule) {
+    cfg.rules = load_batch_rules(o.batch_rules);
+    cfg.soups_per_rule = K;
+    cfg.share_soups = o.soups > 0;
+    const int64_t R = int64_t(cfg.rules.size());
+    if (o.batch > 0 && (K > kBatchMax || o.batch != R * K))
+      throw Error("--batch " + std::to_string(o.batch) + ": " + std::to_string(R) + " rules x " + std::to_string(K) +
+                  " soups make " + std::to_string(R * K) + " universes");
+    in.B = K > kBatchMax ? kBatchMax + 1 : R * K;
+  }
   in.seed = o.seed;
   in.density = o.density;
   const BatchResult r = engine == "hip" ? run_batch_hip(0, cfg, in, o.tune) : run_batch_cpu(o.threads, cfg, in);
@@ -526,10 +591,31 @@ int run_batch(const Options& o) {
   if (!o.batch_csv.empty()) {
     std::ofstream f(o.batch_csv);
     GOL_REQUIRE(f.good(), "--batch-csv: cannot write '" + o.batch_csv + "'");
-    f << "universe,seed,generations,stop,period,population\n";
+    f << (by_rule ? "universe,seed,rule,generations,stop,period,population\n"
+                  : "universe,seed,generations,stop,period,population\n");
     for (int64_t b = 0; b < in.B; ++b)
-      f << b << "," << in.seed + uint64_t(b) << "," << r.generations[size_t(b)] << ","
+      f << b << "," << in.seed + uint64_t(batch_soup(cfg, b)) << ","
+        << (by_rule ? rule_string(batch_rule(cfg, b)) + "," : std::string()) << r.generations[size_t(b)] << ","
         << kBatchStopNames[r.stop[size_t(b)]] << "," << r.period[size_t(b)] << "," << r.population[size_t(b)] << "\n";
+  }
+  if (!o.rules_csv.empty()) {
+    std::ofstream f(o.rules_csv);
+    GOL_REQUIRE(f.good(), "--rules-csv: cannot write '" + o.rules_csv + "'");
+    f << "rule,soups,limit,cycle,extinction,mean_generations,max_generations,max_period,mean_population\n";
+    for (size_t ri = 0; ri < cfg.rules.size(); ++ri) {
+      int64_t c[3] = {0, 0, 0}, gens = 0, pop = 0;
+      int32_t max_gens = 0, max_per = 0;
+      for (size_t b = ri * size_t(K); b < (ri + 1) * size_t(K); ++b) {
+        ++c[r.stop[b]];
+        gens += r.generations[b], pop += r.population[b];
+        max_gens = std::max(max_gens, r.generations[b]), max_per = std::max(max_per, r.period[b]);
+      }
+      char line[256];
+      std::snprintf(line, sizeof line, "%s,%lld,%lld,%lld,%lld,%.6f,%d,%d,%.6f\n", rule_string(cfg.rules[ri]).c_str(),
+                    (long long)K, (long long)c[0], (long long)c[1], (long long)c[2], double(gens) / double(K),
+                    int(max_gens), int(max_per), double(pop) / double(K));
+      f << line;
+    }
   }
   if (!o.metrics.empty()) {
     std::ofstream f(o.metrics);
@@ -539,16 +625,19 @@ int run_batch(const Options& o) {
       << ", \"max_gens\": " << cfg.max_gens << ", \"max_period\": " << cfg.max_period
       << ", \"batch_kernel_ms\": " << r.kernel_ms << ", \"batch_variant\": " << jstr(r.variant)
       << ", \"limit\": " << counts[0] << ", \"cycle\": " << counts[1] << ", \"extinction\": " << counts[2]
-      << ", \"max_generations\": " << longest << "}\n";
+      << ", \"max_generations\": " << longest;
+    if (by_rule) f << ", \"batch_rules\": " << cfg.rules.size() << ", \"batch_soups\": " << K;
+    f << "}\n";
   }
   std::printf("Batch: %lld universes: %lld limit, %lld cycle, %lld extinction; largest generations %d\n",
               (long long)in.B, (long long)counts[0], (long long)counts[1], (long long)counts[2], int(longest));
+  if (by_rule) std::printf("Rules: %lld rules x %lld soups\n", (long long)cfg.rules.size(), (long long)K);
   std::fflush(stdout);
   return 0;
 }
 
 int run(const Options& o) {
-  if (o.batch > 0) return run_batch(o);
+  if (o.batch > 0 || !o.batch_rules.empty()) return run_batch(o);
   // Input 'none' with patterns to place: the grid starts empty.
   const bool empty_start = o.input == "none" && !o.random && !o.places.empty() && o.resume.empty();
   const bool have_input = o.random || !o.input.empty();

@@ -101,6 +101,17 @@ def parse_args(argv=None):
                    help="--batch: the largest period recognised, 1 to 65536 (default 64)")
     p.add_argument("--batch-csv", default=None, metavar="PATH",
                    help="--batch: write 'universe,seed,generations,stop,period,population' lines, one per universe")
+    p.add_argument("--batch-rules", default=None, metavar="FILE|all",
+                   help="--batch with a rule per universe, N = the number of rules R (an explicit --batch N must "
+                        "agree): FILE holds one rule per line (# comments and blank lines skipped), all = the 131072 "
+                        "Life-like rules without B0; universe b runs rule b on seed SEED + b; any rule on either "
+                        "engine; not with --rule; prints a second line 'Rules: R rules x K soups' and adds a 'rule' "
+                        "column after 'seed' to --batch-csv")
+    p.add_argument("--soups", type=int, default=None, metavar="K",
+                   help="--batch-rules: the cross product, N = R * K: universe r*K + j runs rule r on seed SEED + j")
+    p.add_argument("--rules-csv", default=None, metavar="PATH",
+                   help="--batch-rules: write 'rule,soups,limit,cycle,extinction,mean_generations,max_generations,"
+                        "max_period,mean_population' lines, one per rule")
     a = p.parse_args(argv)
     a.output_given = a.output is not None
     a.sim_freq_given = a.sim_freq is not None
@@ -231,10 +242,38 @@ def batch_summary(n: int, counts: dict, longest: int) -> str:
             f"{counts['extinction']} extinction; largest generations {longest}\n")
 
 
+def load_batch_rules(arg: str) -> list[str]:
+    """--batch-rules: the rules of FILE (one per line, # comments and blank
+    lines skipped), or all Life-like rules without B0."""
+    from .models.batch import life_like_rules  # noqa: PLC0415
+
+    if arg == "all":
+        return life_like_rules()
+    try:
+        with open(arg, "r", encoding="ascii", errors="replace") as f:
+            lines = f.read().split("\n")
+    except OSError:
+        raise SystemExit(f"gol: error: --batch-rules: cannot read '{arg}'")
+    rules = []
+    for n, line in enumerate(lines, 1):
+        text = line.partition("#")[0].strip(" \t\r")
+        if not text:
+            continue
+        try:
+            rules.append(parse_rule(text))
+        except RuntimeError as e:
+            raise SystemExit(f"gol: error: --batch-rules {arg}: line {n}: {e}")
+    if not rules:
+        raise SystemExit(f"gol: error: --batch-rules {arg}: the file names no rule")
+    return rules
+
+
 def run_batch(a) -> int:
-    """--batch: one call of simulate_batch, the CSV, the metrics and one summary line."""
+    """--batch: one call of simulate_batch, the CSVs, the metrics and the summary."""
     from .models.batch import simulate_batch  # noqa: PLC0415
 
+    if a.batch_rules is not None and a.rule is not None:
+        raise SystemExit("--batch-rules with --rule: the rules come from the list")
     if a.input_file != "none" or a.random is None:
         raise SystemExit("--batch runs random soups: give the input 'none' and --random SEED[:DENSITY]")
     single = {"--output": a.output_given, "--census": a.census is not None,
@@ -249,14 +288,23 @@ def run_batch(a) -> int:
                              "(its results go to --batch-csv and --metrics-json)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--batch runs on one device: not under torchrun with more than one process")
-    if a.batch < 1:
+    if a.batch is not None and a.batch < 1:
         raise SystemExit("--batch: the number of universes must be at least 1")
+    if a.soups is not None and a.soups < 1:
+        raise SystemExit("--soups: the number of soups per rule must be at least 1")
     if a.engine == "ref":
         raise SystemExit("--batch runs on --engine hip or cpu, not ref")
     s, _, d = a.random.partition(":")
     seed, density = int(s), float(d) if d else 0.5
+    rules, K = None, a.soups or 1
+    if a.batch_rules is not None:
+        rules = load_batch_rules(a.batch_rules)
+        if a.batch is not None and a.batch != len(rules) * K:
+            raise SystemExit(f"gol: error: --batch {a.batch}: {len(rules)} rules x {K} soups make {len(rules) * K} "
+                             "universes")
+        a.batch = len(rules) * K
     try:
-        r = simulate_batch(batch=a.batch, shape=(a.width, a.height), random=(seed, density), max_gens=a.gens,
+        r = simulate_batch(batch=a.batch, rules=rules, soups=a.soups, shape=(a.width, a.height), random=(seed, density), max_gens=a.gens,
                            max_period=64 if a.max_period is None else a.max_period,
                            rule=a.rule if a.rule is not None else DEFAULT_RULE,
                            boundary=a.boundary or DEFAULT_BOUNDARY, engine=a.engine, threads=a.threads,
@@ -266,10 +314,20 @@ def run_batch(a) -> int:
     names = r.stop_names()
     if a.batch_csv is not None:
         with open(a.batch_csv, "w") as f:
-            f.write("universe,seed,generations,stop,period,population\n")
+            f.write(f"universe,seed,{'rule,' if rules else ''}generations,stop,period,population\n")
             for b in range(a.batch):
-                f.write(f"{b},{(seed + b) % 2**64},{int(r.generations[b])},{names[b]},{int(r.period[b])},"
-                        f"{int(r.population[b])}\n")
+                soup = b % K if a.soups is not None else b
+                f.write(f"{b},{(seed + soup) % 2**64},{rules[b // K] + ',' if rules else ''}{int(r.generations[b])},"
+                        f"{names[b]},{int(r.period[b])},{int(r.population[b])}\n")
+    if a.rules_csv is not None:
+        per = r.per_rule()
+        with open(a.rules_csv, "w") as f:
+            f.write("rule,soups,limit,cycle,extinction,mean_generations,max_generations,max_period,mean_population\n")
+            for i, rule in enumerate(rules):
+                c = per["counts"][i]
+                f.write(f"{rule},{K},{int(c[0])},{int(c[1])},{int(c[2])},{per['mean_generations'][i]:.6f},"
+                        f"{int(per['max_generations'][i])},{int(per['max_period'][i])},"
+                        f"{per['mean_population'][i]:.6f}\n")
     counts = r.counts()
     longest = int(r.generations.max())
     write_json(a.metrics_json, {"engine": "cpu" if r.variant.startswith("batch cpu") else "hip", "rule": parse_rule(a.rule) if a.rule is not None else DEFAULT_RULE,
@@ -277,8 +335,11 @@ def run_batch(a) -> int:
                                 "batch": a.batch, "seed": seed, "density": density, "max_gens": a.gens,
                                 "max_period": 64 if a.max_period is None else a.max_period,
                                 "batch_kernel_ms": r.kernel_ms, "batch_variant": r.variant, **counts,
-                                "max_generations": longest})
+                                "max_generations": longest,
+                                **({"batch_rules": len(rules), "batch_soups": K} if rules else {})})
     sys.stdout.write(batch_summary(a.batch, counts, longest))
+    if rules:
+        sys.stdout.write(f"Rules: {len(rules)} rules x {K} soups\n")
     sys.stdout.flush()
     return 0
 
@@ -288,7 +349,9 @@ def main(argv=None) -> int:
     if "help" in a.tune:
         print_tuning_keys()
         return 0
-    if a.batch is not None:
+    if a.batch_rules is None and (a.soups is not None or a.rules_csv is not None):
+        raise SystemExit("--soups and --rules-csv need --batch-rules FILE|all")
+    if a.batch is not None or a.batch_rules is not None:
         return run_batch(a)
     if a.max_period is not None or a.batch_csv is not None:
         raise SystemExit("--max-period and --batch-csv need --batch N")

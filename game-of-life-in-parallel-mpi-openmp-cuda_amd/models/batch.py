@@ -2,9 +2,10 @@
 
 The engine behind ``Simulation`` streams one huge grid; ``simulate_batch``
 runs ``B`` independent universes of one small shape (32 or 64 cells wide, 8,
-16, 32 or 64 high), one rule and one boundary, and reports for each when it
-stopped and into what (csrc/include/gol/batch.hpp has the semantics, the hip
-engine's kernel is csrc/kernels/life_batch.hip).
+16, 32 or 64 high), one boundary and one rule - or, with ``rules=``, a rule per
+universe - and reports for each when it stopped and into what
+(csrc/include/gol/batch.hpp has the semantics, the hip engine's kernel is
+csrc/kernels/life_batch.hip).
 """
 from __future__ import annotations
 
@@ -28,7 +29,9 @@ class BatchResult:
     ``max_period`` (0 at the limit); ``stop``: a code into ``BATCH_STOP``;
     ``population``: live cells of the final grid; ``grids``: the final grids
     ``(B, H, W)``, each at its universe's own stop generation, or ``None``.
-    ``kernel_ms``: the hip engine's one kernel (the cpu engine's loop)."""
+    ``kernel_ms``: the hip engine's one kernel (the cpu engine's loop).
+    ``rules``: the canonical B/S strings of a ``rules=`` run (else ``None``);
+    ``soups``: its ``soups=K`` (else ``None``)."""
     generations: np.ndarray
     period: np.ndarray
     stop: np.ndarray
@@ -36,6 +39,8 @@ class BatchResult:
     grids: np.ndarray | None
     kernel_ms: float
     variant: str
+    rules: list[str] | None = None
+    soups: int | None = None
 
     def stop_names(self) -> list[str]:
         return [BATCH_STOP[int(c)] for c in self.stop]
@@ -44,10 +49,37 @@ class BatchResult:
         """Universes per stop reason."""
         return {name: int((self.stop == code).sum()) for code, name in enumerate(BATCH_STOP)}
 
+    def per_rule(self) -> dict[str, np.ndarray]:
+        """Summaries over the R rules of a ``rules=`` run (row r: universes
+        ``r*K .. r*K + K - 1``, K = ``soups`` or 1): ``counts`` (R, 3) int64 in
+        ``BATCH_STOP`` order, ``mean_generations`` float64, ``max_generations``
+        int32, ``max_period`` int32, ``mean_population`` float64."""
+        if self.rules is None:
+            raise ValueError("per_rule: the batch was not run with rules=")
+        R, K = len(self.rules), self.soups or 1
+        stop = self.stop.reshape(R, K)
+        gens, per, pop = (a.reshape(R, K) for a in (self.generations, self.period, self.population))
+        return {"counts": np.stack([(stop == code).sum(axis=1) for code in range(len(BATCH_STOP))], axis=1).astype(np.int64),
+                "mean_generations": gens.sum(axis=1, dtype=np.int64) / K,
+                "max_generations": gens.max(axis=1).astype(np.int32),
+                "max_period": per.max(axis=1).astype(np.int32),
+                "mean_population": pop.sum(axis=1, dtype=np.int64) / K}
+
+
+def life_like_rules() -> list[str]:
+    """The 131,072 Life-like rules without B0 as canonical B/S strings, in a
+    fixed order: rule ``i`` has birth mask ``(i & 0xFF) << 1`` (bit n: born at
+    n neighbours) and survive mask ``i >> 8``.  B1/S is index 1, B3/S23 is
+    index ``(0b1100 << 8) | 0b100`` = 3076."""
+    births = ["B" + "".join(str(n) for n in range(1, 9) if (i >> (n - 1)) & 1) for i in range(256)]
+    survives = ["/S" + "".join(str(n) for n in range(9) if (i >> n) & 1) for i in range(512)]
+    return [b + s for s in survives for b in births]
+
 
 def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens: int = 1024, max_period: int = 64,
                    rule: str = DEFAULT_RULE, boundary: str = DEFAULT_BOUNDARY, engine: str = "auto",
-                   return_grids: bool = False, threads: int = 0, device: int = 0, tune=None) -> BatchResult:
+                   return_grids: bool = False, threads: int = 0, device: int = 0, tune=None, rules=None,
+                   soups=None) -> BatchResult:
     """Run ``B`` universes until each repeats or reaches ``max_gens``.
 
     Input: ``grids``, a ``(B, H, W)`` array of 0/1, or ``random=(seed,
@@ -59,15 +91,54 @@ def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens:
     than it, and on equality the universe stops with ``generations = t`` and
     ``period = t - s``: the exact minimal period whenever it is at most ``P``.
 
+    ``rules``, a sequence of names or B/S strings, gives every universe a rule
+    of its own; on the hip engine the rules are then data (a table on the
+    device), so any rule without B0 runs there.  Alone it pairs rule ``b``
+    with universe ``b``: ``len(rules) == B``, input as above.  With
+    ``soups=K`` it is the cross product, ``B = R * K``: universe ``r*K + j``
+    runs rule ``r`` on soup ``j``, and the input is ``grids (K, H, W)`` or
+    ``random`` with seeds ``seed .. seed + K - 1`` (``batch``, if given, must
+    be ``R * K``).  ``ValueError``: ``rules`` with a non-default ``rule``,
+    ``soups`` without ``rules``, lengths that do not agree.
+
     Refused, naming the limit: widths other than 32 and 64, heights other
     than 8, 16, 32 and 64, ``B`` outside 1..2^24, ``max_period`` outside
     1..65536, ``max_gens`` outside 1..2^24, B0 rules, cells other than 0/1,
     ``grids`` together with ``random``; on the hip engine a rule that is not
-    compiled for it (``hip_rules()``).  ``engine="auto"``: hip where a device
-    is available, else cpu (any rule)."""
+    compiled for it (``hip_rules()``; ``rules=[...]`` takes any).
+    ``engine="auto"``: hip where a device is available, else cpu (any rule)."""
     C = native()
     if grids is not None and (random is not None or batch is not None):
         raise ValueError("simulate_batch: give either grids or random=(seed, density) with batch=B, not both")
+    canon = K = None
+    extra = {}
+    if rules is not None:
+        if parse_rule(rule) != DEFAULT_RULE:
+            raise ValueError(f"simulate_batch: give either rule={rule!r} or rules=[...], not both")
+        canon = []
+        for i, r in enumerate(rules):
+            try:
+                canon.append(parse_rule(r))
+            except RuntimeError as e:
+                raise RuntimeError(f"batch: rule {i} of the list: {e}") from None
+        if not canon:
+            raise ValueError("simulate_batch: rules is empty")
+        R = len(canon)
+        if soups is not None:
+            K = int(soups)
+            if K < 1:
+                raise ValueError(f"simulate_batch: soups={K}: must be at least 1")
+        form = f"{R} rules" if K is None else f"{R} rules x soups={K}"
+        if grids is not None and np.ndim(grids) == 3:
+            given, want = int(np.shape(grids)[0]), R if K is None else K
+            if given != want:
+                raise ValueError(f"simulate_batch: {form} take grids ({want}, H, W), got {given} grids")
+        elif batch is not None and int(batch) != R * (K or 1):
+            raise ValueError(f"simulate_batch: {form} make batch={R * (K or 1)}, got batch={int(batch)}")
+        batch = None if grids is not None else R * (K or 1)
+        extra = dict(rules=canon, soups=K or 1, share_soups=K is not None)
+    elif soups is not None:
+        raise ValueError("simulate_batch: soups=K goes with rules=[...]")
     if engine == "auto":
         engine = "hip" if C.hip_available() else "cpu"
     if engine not in ("hip", "cpu"):
@@ -85,12 +156,12 @@ def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens:
             if ((g != 0) & (g != 1)).any():
                 raise RuntimeError("batch: the input holds 0 (dead) and 1 (live) only")
             g = g.astype(np.uint8)
-        r = C.simulate_batch(np.ascontiguousarray(g), **common)
+        r = C.simulate_batch(np.ascontiguousarray(g), **common, **extra)
     else:
         if random is None or batch is None or shape is None:
             raise ValueError("simulate_batch: without grids, give batch=B, shape=(W, H) and random=(seed, density)")
         seed, density = random
         W, H = shape
         r = C.simulate_batch(None, batch=int(batch), W=int(W), H=int(H), seed=int(seed), density=float(density),
-                             **common)
-    return BatchResult(*r)
+                             **common, **extra)
+    return BatchResult(*r, rules=canon, soups=K)
