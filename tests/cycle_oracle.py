@@ -7,6 +7,8 @@
       word(y, j): cells (y, 32j .. 32j + 31), cell 32j + b at bit b, 0 beyond W
       r(y) = fmix32(y) | 1, A(j) = splitmix64(j) | 1
 
+* ``fingerprint_at``: the share of a word-aligned window at a global row and
+  word, for grids that are known only as a few islands (tests/far_oracle.py).
 * ``brute_cycle``: steps a grid with a caller-supplied step function, keeps
   every grid in a dict and returns (entry, period) of the first repeat.
 * ``pattern_board``: the 96 x 48 torus of the tests: a T-tetromino (it becomes
@@ -20,8 +22,9 @@ import numpy as np
 M32 = np.uint64(0xFFFFFFFF)
 
 
-def _row_keys(H: int) -> np.ndarray:
-    h = np.arange(H, dtype=np.uint64)
+def _row_keys(H: int, y0: int = 0) -> np.ndarray:
+    """r(y) of rows y0 .. H - 1."""
+    h = np.arange(y0, H, dtype=np.uint64)
     h ^= h >> np.uint64(16)
     h = (h * np.uint64(0x85EBCA6B)) & M32
     h ^= h >> np.uint64(13)
@@ -30,9 +33,10 @@ def _row_keys(H: int) -> np.ndarray:
     return h | np.uint64(1)
 
 
-def _col_keys(n: int) -> np.ndarray:
+def _col_keys(n: int, j0: int = 0) -> np.ndarray:
+    """A(j) of words j0 .. n - 1."""
     with np.errstate(over="ignore"):
-        x = np.arange(n, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        x = np.arange(j0, n, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
         x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         x = x ^ (x >> np.uint64(31))
@@ -49,6 +53,19 @@ def fingerprint(grid: np.ndarray) -> int:
     words = np.packbits(g, axis=1, bitorder="little").view("<u4").astype(np.uint64)
     with np.errstate(over="ignore"):
         terms = words * _row_keys(H)[:, None] * _col_keys(nw)[None, :]
+        return int(terms.sum(dtype=np.uint64))
+
+
+def fingerprint_at(window: np.ndarray, y0: int, word0: int) -> int:
+    """The share of a word-aligned window (its width a multiple of 32) whose
+    first cell is global row y0, global word word0.  F is linear in the words,
+    so a sparse grid's fingerprint is the sum of this over its islands."""
+    g = np.asarray(window) != 0
+    h, w = g.shape
+    assert w % 32 == 0 and y0 >= 0 and word0 >= 0, (w, y0, word0)
+    words = np.packbits(g, axis=1, bitorder="little").view("<u4").astype(np.uint64)
+    with np.errstate(over="ignore"):
+        terms = words * _row_keys(y0 + h, y0)[:, None] * _col_keys(word0 + w // 32, word0)[None, :]
         return int(terms.sum(dtype=np.uint64))
 
 
