@@ -176,11 +176,10 @@ class Backend {
     bool drift = false;
     bool link = false;  // consecutive blocks may run linked (BlockArgs::link)
   };
-  virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req,
-                                     Rule /*rule*/ = Rule{}, Boundary boundary = Boundary::Torus,
-                                     bool /*census*/ = false, bool fingerprint = false) const {
+  virtual KernelChoice choose_kernel(Layout l, int64_t /*rows*/, int64_t /*cols*/, int tmax_req, Rule /*rule*/ = Rule{},
+                                     BlockFeatures f = {}) const {
     // A fingerprint weighs every cell by its column: no drifting frame.
-    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && boundary == Boundary::Torus && !fingerprint};
+    return {tmax_req > 0 ? tmax_req : preferred_tmax(l), drifts(l) && !f.plane && !f.fingerprint};
   }
   // Quiet-tile skipping (BlockArgs::quiet, gol/quiet.hpp).  quiet_mode(): the
   // backend's tuning quiet_skip (0: it has no such kernel or it is off, 1
@@ -216,42 +215,23 @@ class Backend {
   // owned word columns of the tiles it computed them in.
   virtual bool quiet_cols() const { return false; }
   virtual void quiet_cols_counts(int64_t* computed, int64_t* of_tiles) const { *computed = *of_tiles = 0; }
-  // Whether run_block evaluates `rule` (BlockArgs::rule) on tiles of this
-  // layout.  The CPU backend runs any rule without B0; the HIP backend the
-  // rules compiled from csrc/kernels/life_rules.def.  unsupported_rule() is
-  // the message of the engine's refusal.
-  virtual bool supports_rule(Layout, Rule rule) const { return rule_is_default(rule); }
-  virtual std::string unsupported_rule(Layout, Rule rule) const {
-    return "backend " + name() + " does not run rule " + rule_string(rule);
+  // Whether run_block runs `rule` (BlockArgs::rule) with the features `f`
+  // (BlockArgs::plane, census, fingerprint; f.plane goes with boundary `b`) on
+  // tiles of this layout: "" where it does, else the message of the engine's
+  // refusal, which names the combination.  The first cause is reported, in
+  // the order boundary, rule, census, fingerprint.  The CPU backend runs any
+  // rule without B0 with any of them; the HIP backend what hip_refusal() says.
+  virtual std::string refusal(Layout, Rule rule, Boundary b, BlockFeatures f) const {
+    const std::string no = "backend " + name() + " does not run ";
+    if (b != Boundary::Torus) return no + "boundary=" + boundary_name(b);
+    if (!rule_is_default(rule)) return no + "rule " + rule_string(rule);
+    if (f.census) return no + "census=1";
+    if (f.fingerprint) return no + "fingerprint=1";
+    return "";
   }
-  // Whether run_block honours BlockArgs::plane (the bounded plane) on tiles of
-  // this layout with `rule`; unsupported_boundary() is the message of the
-  // engine's refusal and names the combination.
-  virtual bool supports_boundary(Layout, Rule, Boundary b) const { return b == Boundary::Torus; }
-  virtual std::string unsupported_boundary(Layout, Rule, Boundary b) const {
-    return "backend " + name() + " does not run boundary=" + boundary_name(b);
-  }
-  // Description of the kernels that run the bounded plane ("" where the
-  // backend has one kind only).
-  virtual std::string plane_kernel(Layout) const { return ""; }
-  // Whether run_block honours BlockArgs::census (the per-generation population
-  // census) on tiles of this layout with `rule` and boundary `b`;
-  // unsupported_census() is the message of the engine's refusal and names the
-  // combination.
-  virtual bool supports_census(Layout, Rule, Boundary) const { return false; }
-  virtual std::string unsupported_census(Layout, Rule, Boundary) const {
-    return "backend " + name() + " does not run census=1";
-  }
-  // Description of the kernels that run a census engine ("" where the backend
-  // has one kind only).
-  virtual std::string census_kernel(Layout) const { return ""; }
-  // The same trio for BlockArgs::fingerprint (the per-generation grid
-  // fingerprint, gol/fingerprint.hpp); `census`: the engine also runs a census.
-  virtual bool supports_fingerprint(Layout, Rule, Boundary, bool /*census*/) const { return false; }
-  virtual std::string unsupported_fingerprint(Layout, Rule, Boundary, bool /*census*/) const {
-    return "backend " + name() + " does not run fingerprint=1";
-  }
-  virtual std::string fingerprint_kernel(Layout) const { return ""; }
+  // Description of the kernels that run the plane, a census or a fingerprint
+  // engine ("" where the backend has one kind only).
+  virtual std::string feature_kernel(Layout, BlockMode) const { return ""; }
   // Row ring (single-rank torus): a tile whose top Dv halo rows are a second
   // virtual mapping of its last Dv owned rows and whose bottom halo rows map
   // its first ones, so the periodic row halos are always valid and never
@@ -280,8 +260,8 @@ class Backend {
   // Fingerprint share of the tile's owned cells (gol/fingerprint.hpp) added to
   // *out64 (backend memory, zeroed by the caller; stream-ordered): owned row 0
   // is global row global_row0, the first owned cell global cell global_col0 (a
-  // backend may need it to be a multiple of 32: supports_fingerprint's caller
-  // checks the decomposition).
+  // backend may need it to be a multiple of 32: refusal()'s caller checks the
+  // decomposition).
   virtual void fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
                            uint64_t* out64) = 0;
   // The owned rows of tile `src` into `dst`, a buffer of g.bytes() bytes
@@ -348,6 +328,9 @@ bool hip_available();
 // The Life-like rules compiled for the HIP engine besides B3/S23
 // (csrc/kernels/life_rules.def).
 std::vector<Rule> hip_rules();
+// The HIP backend's Backend::refusal(), a pure function of the combination and
+// the tuning's u8_kernel=lds: it needs no device.
+std::string hip_refusal(Layout l, Rule rule, Boundary b, BlockFeatures f, bool u8_lds);
 
 // Counter-based RNG used by init_random (host and device agree bit-for-bit).
 GOL_HD inline uint64_t splitmix64(uint64_t x) {

@@ -523,15 +523,19 @@ class Engine {
   int64_t gen_ = 0;
   int64_t exchanges_ = 0, polls_ = 0, launches_ = 0;
   bool plane_ = false;      // EngineConfig::boundary == Boundary::Dead
-  // EngineConfig::census: the device window of per-generation counts, parallel
-  // to flags_ (same base and length, zeroed with it), and whether a run is
-  // filling it (launches outside a run - step_block - count nothing).
-  Owned<uint64_t> census_;
-  bool census_run_ = false;
-  // EngineConfig::fingerprint: the same for the fingerprint series; the device
-  // word of fingerprint(); find_cycle's copy of the state tile.
-  Owned<uint64_t> fprint_;
-  bool fprint_run_ = false;
+  bool plain_ = true;       // a torus engine with no series: no plane, census or fingerprint
+  // A fused per-generation series (EngineConfig::census, ::fingerprint): the
+  // device window of 64-bit values, parallel to flags_ (same base and length,
+  // zeroed with it), and whether a run is filling it (launches outside a run -
+  // step_block - record nothing).
+  struct Series {
+    const char* name;  // in messages
+    bool on = false;   // the configuration asks for it
+    Owned<uint64_t> win;
+    bool run = false;
+  };
+  Series census_{"census"}, fprint_{"fingerprint"};
+  // The device word of fingerprint(); below, find_cycle's copy of the state tile.
   Owned<uint64_t> fp_dev_;
   // density()'s block map and store_window()'s window on the device (the
   // latter on multi-rank runs only), kept between calls and re-allocated

@@ -53,6 +53,17 @@ struct TileGeom {
   }
 };
 
+// What a temporal block fuses into its generations beside the change flags:
+// the bounded plane's edge mask, the census, the fingerprint (BlockArgs below,
+// EngineConfig).  Every layer asks about the three through this one value.
+struct BlockFeatures {
+  bool plane = false, census = false, fingerprint = false;
+  bool series() const { return census || fingerprint; }  // a 64-bit value per generation
+  bool any() const { return plane || series(); }
+};
+// One of them, or none: what names a kernel family (Backend::feature_kernel).
+enum class BlockMode : int { Plain, Plane, Census, Fingerprint };
+
 // One temporal block: T generations evaluated in a single pass over the tile.
 // Output rows are [row_lo, row_hi) (padded coordinates); the input must hold
 // valid cells on [row_lo - T, row_hi + T).  The per-generation "changed" flags
@@ -134,6 +145,7 @@ struct BlockArgs {
   // quiet or gen_dev; a HIP launch takes a census or a fingerprint, not both.
   uint64_t* fingerprint = nullptr;
   int64_t global_row0 = 0, global_col0 = 0;
+  BlockFeatures features() const { return {plane, census != nullptr, fingerprint != nullptr}; }
 };
 
 }  // namespace gol

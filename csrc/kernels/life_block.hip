@@ -47,6 +47,29 @@ const RuleKernels* rule_kernels(Rule r) {
   return nullptr;
 }
 
+// The feature kernels (BlockArgs::features), a family per mode: B3/S23 on the
+// DPP window, T <= 16, never linked, chained or skipping.
+struct ModeRow {
+  const char* word;  // in the variant string, and "<word> kernels"
+  const char* what;  // the launch in the launcher's messages
+  const char* note;  // where a forced adder window has no kernels
+  VariantFn bits, u8;
+};
+const ModeRow kModes[] = {
+    {},  // BlockMode::Plain: launch_life_block picks among the variants itself
+    {"plane", "boundary=dead", "on the plane", launch_plane_bits_dpp, launch_plane_u8_dpp},
+    {"census", "census", "with the census", launch_census_bits_dpp, launch_census_u8_dpp},
+    {"fingerprint", "fingerprint", "with the fingerprint", launch_fprint_bits_dpp, launch_fprint_u8_dpp},
+};
+
+// A launch fuses one of them at most.
+BlockMode block_mode(const BlockArgs& a) {
+  const BlockFeatures f = a.features();
+  GOL_REQUIRE(!(f.census && f.fingerprint), "life_block: census and fingerprint in one launch");
+  GOL_REQUIRE(!(f.plane && f.series()), "life_block: boundary=dead with a census or a fingerprint in one launch");
+  return f.plane ? BlockMode::Plane : f.census ? BlockMode::Census : f.fingerprint ? BlockMode::Fingerprint : BlockMode::Plain;
+}
+
 }  // namespace
 
 std::vector<Rule> life_block_rules() {
@@ -57,37 +80,22 @@ std::vector<Rule> life_block_rules() {
 
 bool life_block_has_rule(Rule r) { return rule_is_default(r) || rule_kernels(r) != nullptr; }
 
-std::string life_block_variant(Layout layout, const LifeTuning& tune) {
+std::string life_block_variant(Layout layout, const LifeTuning& tune, BlockMode mode) {
+  const bool grouped = tune.group != 0;
+  const std::string lay = layout == Layout::Bits ? "bits" : "u8";
+  const std::string group =
+      grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "";
+  if (mode != BlockMode::Plain) {
+    const ModeRow& m = kModes[int(mode)];
+    return lay + " wpl=1 dpp " + m.word +
+           (tune.xlane == kXlaneAdd ? std::string(" (xlane=add runs dpp: no adder window ") + m.note + ")" : "") + group +
+           (mode != BlockMode::Plane ? std::string(tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)" : "");
+  }
   if (layout == Layout::U8 && tune.u8_lds)
     return tune.lds_T > 1 ? "u8 lds-tiled T=" + std::to_string(tune.lds_T) + (tune.lds_pack && tune.lds_T >= 8 ? " packed" : "")
                           : std::string("u8 lds-tiled single-step");
-  const bool grouped = tune.group != 0;
-  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 " + xlane_name(tune.xlane) +
-         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "") +
+  return lay + " wpl=1 " + xlane_name(tune.xlane) + group +
          (grouped && tune.chain == 1 ? " chain" : grouped && tune.chain < 0 ? " chain=tuned" : "");
-}
-
-std::string life_block_plane_variant(Layout layout, const LifeTuning& tune) {
-  const bool grouped = tune.group != 0;
-  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp plane" +
-         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window on the plane)" : "") +
-         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "");
-}
-
-std::string life_block_census_variant(Layout layout, const LifeTuning& tune) {
-  const bool grouped = tune.group != 0;
-  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp census" +
-         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window with the census)" : "") +
-         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "") +
-         (tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)";
-}
-
-std::string life_block_fprint_variant(Layout layout, const LifeTuning& tune) {
-  const bool grouped = tune.group != 0;
-  return std::string(layout == Layout::Bits ? "bits" : "u8") + " wpl=1 dpp fingerprint" +
-         (tune.xlane == kXlaneAdd ? " (xlane=add runs dpp: no adder window with the fingerprint)" : "") +
-         (grouped ? (tune.group < 0 ? std::string(" group=auto") : " group=" + std::to_string(tune.group)) : "") +
-         (tune.wrap ? " wrap" : "") + " (no fold, link, chain or skipping)";
 }
 
 int life_block_max_T(Layout layout, const LifeTuning& tune) {
@@ -133,74 +141,60 @@ LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const
   p.link_ring_rows = a.ring && a.row_lo == g.Dv && a.row_hi == g.Dv + g.H ? g.H : 0;
   p.fault_delay = tune.fault_delay;
   const int64_t rows = a.row_hi - a.row_lo;
-  if (a.plane) {
-    // The bounded plane: lb::PlaneIO kernels, B3/S23 on the DPP window (a
-    // forced adder window runs the DPP window too: its drifting frame is a
-    // relabelling of torus columns).  The engine refuses the combinations that
-    // have no plane kernel before any launch; these guard the launcher itself.
-    GOL_REQUIRE(rule_is_default(a.rule), "life_block: boundary=dead runs B3/S23 only on the HIP engine");
-    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: boundary=dead with u8_kernel=lds");
-    GOL_REQUIRE(!a.allow_drift && !a.full_width && !a.wrap_rows && !a.ring && !a.link && !a.quiet,
-                "life_block: boundary=dead with a torus-only launch option");
-    GOL_REQUIRE(a.T <= 16, "life_block: plane kernels run temporal blocks of at most 16 generations");
-    GOL_REQUIRE(g.R() < (int64_t(1) << 30), "life_block: boundary=dead needs fewer than 2^30 tile rows");
-    GOL_REQUIRE(a.grid_row_lo >= 0 && a.grid_row_lo < a.grid_row_hi && a.grid_row_hi <= g.R() &&
-                    a.grid_cell_lo >= 0 && a.grid_cell_lo % 32 == 0 && a.grid_cell_lo < a.grid_cell_hi &&
-                    a.grid_cell_hi <= 32 * g.Wp(),
-                "life_block: grid bounds outside the tile");
-    p.wrap_w = 0;
+  const BlockMode mode = block_mode(a);
+  if (mode != BlockMode::Plain) {
+    // The plane, census and fingerprint kernels (lb::PlaneIO, CensusIO,
+    // FingerprintIO): B3/S23 on the DPP window (a forced adder window runs the
+    // DPP window too: its drifting frame is a relabelling of torus columns).
+    // The engine refuses the combinations that have no such kernel before any
+    // launch; these guard the launcher itself.
+    const ModeRow& m = kModes[int(mode)];
+    const bool series = mode != BlockMode::Plane;
+    const auto msg = [&m](const char* tail) { return std::string("life_block: ") + m.what + tail; };
+    GOL_REQUIRE(rule_is_default(a.rule), msg(" runs B3/S23 only on the HIP engine"));
+    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), msg(" with u8_kernel=lds"));
+    // A series keeps wrapped column reads and the row ring: the owned words and
+    // rows are counted once either way.
+    GOL_REQUIRE(!a.allow_drift && !a.wrap_rows && !a.link && !a.quiet && (series ? !a.gen_dev : !a.full_width && !a.ring),
+                msg(series ? " with a launch option it does not run with" : " with a torus-only launch option"));
+    GOL_REQUIRE(a.T <= 16, std::string("life_block: ") + m.word + " kernels run temporal blocks of at most 16 generations");
     p.link_ring_rows = 0;
-    p.grid_row_lo = int(a.grid_row_lo);
-    p.grid_row_hi = int(a.grid_row_hi);
-    p.grid_w0 = int(a.grid_cell_lo / 32);
-    p.grid_w1 = int(ceil_div(a.grid_cell_hi, 32));
-    const int64_t gtail = a.grid_cell_hi % 32;
-    p.grid_last_mask = gtail ? (0xFFFFFFFFu >> (32 - gtail)) : 0xFFFFFFFFu;
-    return (g.layout == Layout::U8 ? launch_plane_u8_dpp : launch_plane_bits_dpp)(p, rows, a.T, tune, ctx, stream);
-  }
-  if (a.census) {
-    // The census: lb::CensusIO kernels, B3/S23 on the torus with the DPP window
-    // (a forced adder window runs the DPP window too).  Wrapped column reads
-    // and the row ring stay: the owned words and rows are counted once either
-    // way.  The engine refuses the combinations that have no census kernel
-    // before any launch; these guard the launcher itself.
-    GOL_REQUIRE(rule_is_default(a.rule), "life_block: census runs B3/S23 only on the HIP engine");
-    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: census with u8_kernel=lds");
-    GOL_REQUIRE(!a.allow_drift && !a.wrap_rows && !a.link && !a.quiet && !a.gen_dev,
-                "life_block: census with a launch option it does not run with");
-    GOL_REQUIRE(a.T <= 16, "life_block: census kernels run temporal blocks of at most 16 generations");
-    // A wave's count of one generation stays below 2^31 (64 lanes x 32 cells x rows).
-    GOL_REQUIRE(rows + 2 * a.T < (int64_t(1) << 20), "life_block: census needs blocks of fewer than 2^20 rows");
-    GOL_REQUIRE(a.gen_base >= a.flags_base, "life_block: census block before its window");
-    GOL_REQUIRE(!a.fingerprint, "life_block: census and fingerprint in one launch");
-    p.link_ring_rows = 0;
-    p.grid_row_lo = int(g.Dv);
-    p.grid_row_hi = int(g.Dv + g.H);
-    p.census = reinterpret_cast<unsigned long long*>(a.census) + (a.gen_base + 1 - a.flags_base);
-    return (g.layout == Layout::U8 ? launch_census_u8_dpp : launch_census_bits_dpp)(p, rows, a.T, tune, ctx, stream);
-  }
-  if (a.fingerprint) {
-    // The fingerprint: lb::FingerprintIO kernels, launched like the census
-    // kernels above.  Rows and words travel in 32 bits; the tile's first owned
-    // column is a word boundary of the global grid (the engine refuses a byte
-    // decomposition where it is not).
-    GOL_REQUIRE(rule_is_default(a.rule), "life_block: fingerprint runs B3/S23 only on the HIP engine");
-    GOL_REQUIRE(!(g.layout == Layout::U8 && tune.u8_lds), "life_block: fingerprint with u8_kernel=lds");
-    GOL_REQUIRE(!a.allow_drift && !a.wrap_rows && !a.link && !a.quiet && !a.gen_dev,
-                "life_block: fingerprint with a launch option it does not run with");
-    GOL_REQUIRE(a.T <= 16, "life_block: fingerprint kernels run temporal blocks of at most 16 generations");
-    GOL_REQUIRE(a.gen_base >= a.flags_base, "life_block: fingerprint block before its window");
-    GOL_REQUIRE(a.global_col0 % 32 == 0, "life_block: fingerprint tile off the global word grid");
-    GOL_REQUIRE(a.global_row0 >= 0 && a.global_row0 + g.R() < (int64_t(1) << 31) &&
-                    a.global_col0 / 32 + g.Wp() < (int64_t(1) << 31),
-                "life_block: fingerprint needs global rows and words below 2^31");
-    p.link_ring_rows = 0;
-    p.grid_row_lo = int(g.Dv);
-    p.grid_row_hi = int(g.Dv + g.H);
-    p.fingerprint = reinterpret_cast<unsigned long long*>(a.fingerprint) + (a.gen_base + 1 - a.flags_base);
-    p.fp_row0 = int(a.global_row0 - g.Dv);
-    p.fp_word0 = int(a.global_col0 / 32);
-    return (g.layout == Layout::U8 ? launch_fprint_u8_dpp : launch_fprint_bits_dpp)(p, rows, a.T, tune, ctx, stream);
+    if (!series) {
+      GOL_REQUIRE(g.R() < (int64_t(1) << 30), "life_block: boundary=dead needs fewer than 2^30 tile rows");
+      GOL_REQUIRE(a.grid_row_lo >= 0 && a.grid_row_lo < a.grid_row_hi && a.grid_row_hi <= g.R() &&
+                      a.grid_cell_lo >= 0 && a.grid_cell_lo % 32 == 0 && a.grid_cell_lo < a.grid_cell_hi &&
+                      a.grid_cell_hi <= 32 * g.Wp(),
+                  "life_block: grid bounds outside the tile");
+      p.wrap_w = 0;
+      p.grid_row_lo = int(a.grid_row_lo);
+      p.grid_row_hi = int(a.grid_row_hi);
+      p.grid_w0 = int(a.grid_cell_lo / 32);
+      p.grid_w1 = int(ceil_div(a.grid_cell_hi, 32));
+      const int64_t gtail = a.grid_cell_hi % 32;
+      p.grid_last_mask = gtail ? (0xFFFFFFFFu >> (32 - gtail)) : 0xFFFFFFFFu;
+    } else {
+      GOL_REQUIRE(a.gen_base >= a.flags_base, msg(" block before its window"));
+      p.grid_row_lo = int(g.Dv);
+      p.grid_row_hi = int(g.Dv + g.H);
+      const int64_t slot = a.gen_base + 1 - a.flags_base;
+      if (mode == BlockMode::Census) {
+        // A wave's count of one generation stays below 2^31 (64 lanes x 32 cells x rows).
+        GOL_REQUIRE(rows + 2 * a.T < (int64_t(1) << 20), "life_block: census needs blocks of fewer than 2^20 rows");
+        p.census = reinterpret_cast<unsigned long long*>(a.census) + slot;
+      } else {
+        // Rows and words travel in 32 bits; the tile's first owned column is a
+        // word boundary of the global grid (the engine refuses a byte
+        // decomposition where it is not).
+        GOL_REQUIRE(a.global_col0 % 32 == 0, "life_block: fingerprint tile off the global word grid");
+        GOL_REQUIRE(a.global_row0 >= 0 && a.global_row0 + g.R() < (int64_t(1) << 31) &&
+                        a.global_col0 / 32 + g.Wp() < (int64_t(1) << 31),
+                    "life_block: fingerprint needs global rows and words below 2^31");
+        p.fingerprint = reinterpret_cast<unsigned long long*>(a.fingerprint) + slot;
+        p.fp_row0 = int(a.global_row0 - g.Dv);
+        p.fp_word0 = int(a.global_col0 / 32);
+      }
+    }
+    return (g.layout == Layout::U8 ? m.u8 : m.bits)(p, rows, a.T, tune, ctx, stream);
   }
   int x = tune.xlane == kXlaneAdd || tune.xlane == kXlaneAuto ? tune.xlane : kXlaneDpp;
   // Any rule but B3/S23: the kernels compiled from life_rules.def.

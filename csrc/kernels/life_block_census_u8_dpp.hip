@@ -1,4 +1,4 @@
 // Census kernels (per-generation live-cell counts), variant u8_dpp: see life_block_launch.hpp.
 #include "life_block_launch.hpp"
 
-GOL_CENSUS_TU_U8_DPP
+GOL_FEATURE_TU(lb::CensusIO, census, u8_dpp)

@@ -1,4 +1,4 @@
 // Fingerprint kernels (per-generation grid fingerprints), variant u8_dpp: see life_block_launch.hpp.
 #include "life_block_launch.hpp"
 
-GOL_FPRINT_TU_U8_DPP
+GOL_FEATURE_TU(lb::FingerprintIO, fprint, u8_dpp)

@@ -550,6 +550,11 @@ struct FingerprintIO : IO {
 // fingerprint): such a launch is never folded, linked, chained or deep.
 template <class IO>
 inline constexpr bool kSeries = IO::kCensus || IO::kFprint;
+// The plain B3/S23 torus kernels: no rule of life_rules.def, no plane, no
+// series.  Only they are linked or chained, and only their byte layout runs
+// the deep passes.
+template <class IO>
+inline constexpr bool kPlainConway = IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO>;
 
 // Fingerprint (gol/fingerprint.hpp): the census's reduction, weighted by where
 // each cell is.  Every level body adds word * r(y) to a per-level, per-lane

@@ -149,8 +149,7 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
   // tiles, whose launches alone hold 2 waves per SIMD).  Any other launch
   // first joins the two streams.
   if (ctx.link) {
-    if constexpr (IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && IO::kBits && IO::W == 1 &&
-                  (T == 8 || T == 12 || T == 16) &&
+    if constexpr (kPlainConway<IO> && IO::kBits && IO::W == 1 && (T == 8 || T == 12 || T == 16) &&
                   (IO::XL == kXlaneDpp || IO::XL == kXlaneAdd)) {
       if (tune.group != 0) {
         // Blocks of T <= 8 link 4-wave groups where the unlinked path would
@@ -200,7 +199,7 @@ LaunchResult launch_T(LifeBlockParams p, int64_t out_rows, const LifeTuning& tun
       // Rule kernels (IO::Rule other than Conway) are never linked or chained.
       // Neither are the plane's kernels (lb::PlaneIO), the census kernels
       // (lb::CensusIO) or the fingerprint kernels (lb::FingerprintIO).
-      if (IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && ctx.chain) {
+      if (kPlainConway<IO> && ctx.chain) {
         LifeBlockParams ch = p;
         ch.fold = 1;
         ch.fold_lanes = 64;
@@ -271,11 +270,11 @@ LaunchResult launch_variant(const LifeBlockParams& p, int64_t out_rows, int T, c
     case 16: return launch_T<16, IO>(p, out_rows, tune, ctx, s);
     case 24:  // byte layout only: fewer byte-grid passes per generation
       // (the adder window never runs T > 16: launch_life_block switches it to DPP)
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO>)
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && kPlainConway<IO>)
         return launch_deep<24, IO>(p, out_rows, tune, ctx, s);
       [[fallthrough]];
     case 32:
-      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO>) {
+      if constexpr (!IO::kBits && IO::XL != kXlaneAdd && kPlainConway<IO>) {
         if (T == 32) return launch_deep<32, IO>(p, out_rows, tune, ctx, s);
       }
       [[fallthrough]];
@@ -317,46 +316,17 @@ namespace rules {
 #define GOL_RULE_TU_BITS_ADD(name) GOL_RULE_TU(name, bits_add, GOL_RULE_IO_BITS, kXlaneAdd)
 #define GOL_RULE_TU_U8_DPP(name) GOL_RULE_TU(name, u8_dpp, GOL_RULE_IO_U8, kXlaneDpp)
 
-// Bounded-plane kernels (lb::PlaneIO): B3/S23, the DPP window, in the T and
-// classic / grouped variants of a rule translation unit;
-// life_block_plane_<variant>.hip, each one line:
-//   GOL_PLANE_TU_BITS_DPP | GOL_PLANE_TU_U8_DPP
-#define GOL_PLANE_TU(variant, IO_)                                                       \
-  namespace gol {                                                                        \
-  namespace hipk {                                                                       \
-  GOL_LIFE_VARIANT(launch_plane_##variant) {                                             \
-    return lb::launch_variant<lb::PlaneIO<IO_>>(p, out_rows, T, tune, ctx, s);           \
-  }                                                                                      \
-  }                                                                                      \
+// Feature kernels (lb::PlaneIO, lb::CensusIO, lb::FingerprintIO around a B3/S23
+// IO): the DPP window, in the T and classic / grouped variants of a rule
+// translation unit; life_block_<name>_<variant>.hip, each one line:
+//   GOL_FEATURE_TU(lb::PlaneIO | lb::CensusIO | lb::FingerprintIO, plane | census | fprint, bits_dpp | u8_dpp)
+#define GOL_FEATURE_IO_bits_dpp GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway)
+#define GOL_FEATURE_IO_u8_dpp GOL_RULE_IO_U8(kXlaneDpp, lb::Conway)
+#define GOL_FEATURE_TU(wrapper, name, variant)                                                     \
+  namespace gol {                                                                                  \
+  namespace hipk {                                                                                 \
+  GOL_LIFE_VARIANT(launch_##name##_##variant) {                                                    \
+    return lb::launch_variant<wrapper<GOL_FEATURE_IO_##variant>>(p, out_rows, T, tune, ctx, s);    \
+  }                                                                                                \
+  }                                                                                                \
   }
-#define GOL_PLANE_TU_BITS_DPP GOL_PLANE_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
-#define GOL_PLANE_TU_U8_DPP GOL_PLANE_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))
-
-// Census kernels (lb::CensusIO): B3/S23 on the torus, the DPP window, in the T
-// and classic / grouped variants of a rule translation unit;
-// life_block_census_<variant>.hip, each one line:
-//   GOL_CENSUS_TU_BITS_DPP | GOL_CENSUS_TU_U8_DPP
-#define GOL_CENSUS_TU(variant, IO_)                                                      \
-  namespace gol {                                                                        \
-  namespace hipk {                                                                       \
-  GOL_LIFE_VARIANT(launch_census_##variant) {                                            \
-    return lb::launch_variant<lb::CensusIO<IO_>>(p, out_rows, T, tune, ctx, s);          \
-  }                                                                                      \
-  }                                                                                      \
-  }
-#define GOL_CENSUS_TU_BITS_DPP GOL_CENSUS_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
-#define GOL_CENSUS_TU_U8_DPP GOL_CENSUS_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))
-
-// Fingerprint kernels (lb::FingerprintIO): as the census kernels;
-// life_block_fprint_<variant>.hip, each one line:
-//   GOL_FPRINT_TU_BITS_DPP | GOL_FPRINT_TU_U8_DPP
-#define GOL_FPRINT_TU(variant, IO_)                                                      \
-  namespace gol {                                                                        \
-  namespace hipk {                                                                       \
-  GOL_LIFE_VARIANT(launch_fprint_##variant) {                                            \
-    return lb::launch_variant<lb::FingerprintIO<IO_>>(p, out_rows, T, tune, ctx, s);     \
-  }                                                                                      \
-  }                                                                                      \
-  }
-#define GOL_FPRINT_TU_BITS_DPP GOL_FPRINT_TU(bits_dpp, GOL_RULE_IO_BITS(kXlaneDpp, lb::Conway))
-#define GOL_FPRINT_TU_U8_DPP GOL_FPRINT_TU(u8_dpp, GOL_RULE_IO_U8(kXlaneDpp, lb::Conway))

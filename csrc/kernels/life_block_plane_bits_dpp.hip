@@ -1,4 +1,4 @@
 // Bounded-plane kernels (dead edges), variant bits_dpp: see life_block_launch.hpp.
 #include "life_block_launch.hpp"
 
-GOL_PLANE_TU_BITS_DPP
+GOL_FEATURE_TU(lb::PlaneIO, plane, bits_dpp)

@@ -347,7 +347,7 @@ void life_group_kernel(const LifeBlockParams p) {
   // control flow is the same for all of them; lanes carry their group's row
   // offset in their read / store offsets.
   // fold == 1 (launch_T); rule, plane, census and fingerprint kernels are never chained (the wait compiles out)
-  const bool chain = IO::Rule::kDefault && !IO::Edge::kPlane && !kSeries<IO> && p.chain_buf != nullptr;
+  const bool chain = kPlainConway<IO> && p.chain_buf != nullptr;
   int kcol, grp, nsub = 1, sub_lanes = 64;
   if (p.fold > 1 && blk >= (p.ncolw - 1) * p.nseg) {
     kcol = p.ncolw - 1;

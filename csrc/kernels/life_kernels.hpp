@@ -359,14 +359,9 @@ LaunchResult launch_life_block(const BlockArgs& a, const LifeTuning& tune, const
 // (life_rules.def), and whether launch_life_block runs `r`.
 std::vector<Rule> life_block_rules();
 bool life_block_has_rule(Rule r);
-// Description of the kernel variant the tuning selects for a layout.
-std::string life_block_variant(Layout layout, const LifeTuning& tune);
-// The same for a bounded-plane engine (BlockArgs::plane).
-std::string life_block_plane_variant(Layout layout, const LifeTuning& tune);
-// The same for a census engine (BlockArgs::census).
-std::string life_block_census_variant(Layout layout, const LifeTuning& tune);
-// The same for a fingerprint engine (BlockArgs::fingerprint).
-std::string life_block_fprint_variant(Layout layout, const LifeTuning& tune);
+// Description of the kernel variant the tuning selects for a layout, and of
+// the one a plane, census or fingerprint engine runs (BlockArgs::features).
+std::string life_block_variant(Layout layout, const LifeTuning& tune, BlockMode mode = BlockMode::Plain);
 // Largest T that keeps 2 waves/SIMD for the variant's words-per-lane.
 int life_block_max_T(Layout layout, const LifeTuning& tune);
 
@@ -378,17 +373,15 @@ GOL_LIFE_VARIANT(launch_bits_w1_dpp);
 GOL_LIFE_VARIANT(launch_u8_w1_dpp);
 GOL_LIFE_VARIANT(launch_bits_w1_add);
 GOL_LIFE_VARIANT(launch_u8_w1_add);
-// The bounded plane (lb::PlaneIO; life_block_plane_*.hip): DPP window only -
-// the adder window's drifting frame is a relabelling of torus columns.
+// The feature kernels (life_block_<name>_*.hip, launch_life_block's kModes):
+// the bounded plane (lb::PlaneIO), the census (lb::CensusIO) and the
+// fingerprint (lb::FingerprintIO), scheduled like the census.  DPP window only:
+// the adder window's drifting frame is a relabelling of torus columns (it
+// would count exactly too, but it is a second set of kernels).
 GOL_LIFE_VARIANT(launch_plane_bits_dpp);
 GOL_LIFE_VARIANT(launch_plane_u8_dpp);
-// The census (lb::CensusIO; life_block_census_*.hip): DPP window only - the
-// adder window would count exactly too (its frame is a relabelling of
-// columns), but it is a second set of kernels.
 GOL_LIFE_VARIANT(launch_census_bits_dpp);
 GOL_LIFE_VARIANT(launch_census_u8_dpp);
-// The per-generation grid fingerprint (lb::FingerprintIO;
-// life_block_fprint_*.hip): scheduled like the census.
 GOL_LIFE_VARIANT(launch_fprint_bits_dpp);
 GOL_LIFE_VARIANT(launch_fprint_u8_dpp);
 // The quiet-tile skipping kernel (bit layout, DPP window, T = 12, 4-wave

@@ -213,15 +213,11 @@ class CpuBackend final : public Backend {
     return drift_ ? "cpu [drift]" : "cpu";
   }
   bool drifts(Layout) const override { return drift_; }
-  // Any Life-like rule (B0 is refused by the engine itself).
-  bool supports_rule(Layout, Rule) const override { return true; }
-  // The bounded plane with any rule (run_block masks every level row).
-  bool supports_boundary(Layout, Rule, Boundary) const override { return true; }
-  // The census with any rule, on the torus and the plane (run_block counts
-  // the level rows of its bands).
-  bool supports_census(Layout, Rule, Boundary) const override { return true; }
-  // The fingerprint likewise, with or without the census, at any tile offset.
-  bool supports_fingerprint(Layout, Rule, Boundary, bool) const override { return true; }
+  // Any Life-like rule (B0 is refused by the engine itself), on the torus and
+  // the bounded plane (run_block masks every level row), with the census (it
+  // counts the level rows of its bands), the fingerprint (at any tile offset)
+  // or both.
+  std::string refusal(Layout, Rule, Boundary, BlockFeatures) const override { return ""; }
   void fingerprint(const void* buf, const TileGeom& g, int64_t global_row0, int64_t global_col0,
                    uint64_t* out64) override;
   void tiles_differ(const void* a, const void* b, const TileGeom& g, uint32_t* flag) override;

@@ -641,12 +641,10 @@ class HipBackend final : public Backend {
       check_ptr(a.out, "run_block output");
     }
     const bool capturing = capturing_;  // capture_begin / capture_end (no query per launch)
-    // Rule kernels (any rule but B3/S23) are never linked or chained, forced
-    // link=1 / chain=1 included.
-    // Nor are the plane's kernels (BlockArgs::plane), which never skip either.
-    // The census kernels (BlockArgs::census) likewise.
-    // And the fingerprint kernels (BlockArgs::fingerprint).
-    const bool conway = rule_is_default(a.rule) && !a.plane && !a.census && !a.fingerprint;
+    // Rule kernels (any rule but B3/S23) and the plane, census and fingerprint
+    // kernels (BlockArgs::features) are never linked or chained, forced
+    // link=1 / chain=1 included, and never skip.
+    const bool conway = rule_is_default(a.rule) && !a.features().any();
     // Wave trace: launch trace_at_ (its `pair` form: and the next one).
     const int64_t traced = trace_at_ < 0 ? -1 : launches_ - trace_at_;
     const bool trace = traced == 0 || (traced == 1 && trace_pair_);
@@ -801,23 +799,22 @@ class HipBackend final : public Backend {
   // same window and T: their adder kernels keep four waves per SIMD at T = 12
   // (docs/PERFORMANCE.md "Life-like rules").  Their byte kernels stop at
   // T = 16, and they never link.
-  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule, Boundary boundary,
-                             bool census, bool fingerprint) const override {
-    // The bounded plane: the DPP window's choice of T (its kernels stop at
-    // T = 16 in both layouts), never drifting, never linked, never skipping.
-    // The census: the same (its kernels are the DPP window's, T <= 16).
-    // The fingerprint: as the census.
-    if (boundary == Boundary::Dead || census || fingerprint) {
+  KernelChoice choose_kernel(Layout l, int64_t rows, int64_t cols, int tmax_req, Rule rule,
+                             BlockFeatures f) const override {
+    // The plane, the census and the fingerprint: the DPP window's choice of T
+    // (their kernels stop at T = 16 in both layouts), never drifting, never
+    // linked, never skipping.
+    if (f.any()) {
       KernelChoice k = choose_conway(l, rows, cols, tmax_req, hipk::kXlaneDpp);
       k.tmax = std::min(k.tmax, 16);
       // The bit layout's T = 16 census kernel takes 153 VGPRs (3 waves per
       // SIMD) where T = 12 takes 122 (4 waves): 32768^2 15.48 against 14.08 ms
       // per 1000 generations (docs/PERFORMANCE.md "Population census").
-      if (census && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
+      if (f.census && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
       // The bit layout's fingerprint kernels take 181 VGPRs at T = 16 (2 waves
       // per SIMD), 141 at T = 12 (3 waves) and 102 at T = 8 (4 waves): the
       // census's 12 until measured (docs/PERFORMANCE.md "Cycle detection").
-      if (fingerprint && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
+      if (f.fingerprint && tmax_req <= 0 && l == Layout::Bits && k.tmax == 16) k.tmax = 12;
       k.drift = k.link = false;
       return k;
     }
@@ -835,67 +832,10 @@ class HipBackend final : public Backend {
     }
     return k;
   }
-  bool supports_rule(Layout l, Rule rule) const override {
-    if (rule_is_default(rule)) return true;
-    return hipk::life_block_has_rule(rule) && !(l == Layout::U8 && tune_.u8_lds);
+  std::string refusal(Layout l, Rule rule, Boundary b, BlockFeatures f) const override {
+    return hip_refusal(l, rule, b, f, tune_.u8_lds);
   }
-  std::string unsupported_rule(Layout l, Rule rule) const override {
-    if (l == Layout::U8 && tune_.u8_lds && hipk::life_block_has_rule(rule))
-      return "rule " + rule_string(rule) + ": the LDS-tiled byte kernels (tuning u8_kernel=lds) run B3/S23 only";
-    std::string have = "B3/S23";
-    for (const Rule r : hipk::life_block_rules()) have += ", " + rule_string(r);
-    return "rule " + rule_string(rule) + " is not compiled for the HIP engine (compiled: " + have +
-           "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)";
-  }
-  bool supports_boundary(Layout l, Rule rule, Boundary b) const override {
-    return b == Boundary::Torus || (rule_is_default(rule) && !(l == Layout::U8 && tune_.u8_lds));
-  }
-  std::string unsupported_boundary(Layout l, Rule rule, Boundary b) const override {
-    if (l == Layout::U8 && tune_.u8_lds)
-      return std::string("boundary=") + boundary_name(b) +
-             " with u8_kernel=lds: the LDS-tiled byte kernels wrap their reads around the torus";
-    return std::string("boundary=") + boundary_name(b) + " with rule " + rule_string(rule) +
-           " on the HIP engine: the plane kernels are compiled for B3/S23 only (the cpu and ref engines run any "
-           "rule on the plane)";
-  }
-  std::string plane_kernel(Layout l) const override { return hipk::life_block_plane_variant(l, tune_); }
-  // The census: B3/S23 on the torus, the temporal-block kernels of either layout.
-  bool supports_census(Layout l, Rule rule, Boundary b) const override {
-    return b == Boundary::Torus && rule_is_default(rule) && !(l == Layout::U8 && tune_.u8_lds);
-  }
-  std::string unsupported_census(Layout l, Rule rule, Boundary b) const override {
-    if (b != Boundary::Torus)
-      return std::string("census=1 with boundary=") + boundary_name(b) +
-             " on the HIP engine: the census kernels are compiled for the torus only (the cpu and ref engines "
-             "count on the plane)";
-    if (!rule_is_default(rule))
-      return "census=1 with rule " + rule_string(rule) +
-             " on the HIP engine: the census kernels are compiled for B3/S23 only (the cpu and ref engines count "
-             "under any rule)";
-    (void)l;
-    return "census=1 with u8_kernel=lds: the LDS-tiled byte kernels have no census";
-  }
-  std::string census_kernel(Layout l) const override { return hipk::life_block_census_variant(l, tune_); }
-  // The fingerprint: what the census runs on, and not together with it.
-  bool supports_fingerprint(Layout l, Rule rule, Boundary b, bool census) const override {
-    return !census && supports_census(l, rule, b);
-  }
-  std::string unsupported_fingerprint(Layout l, Rule rule, Boundary b, bool census) const override {
-    if (b != Boundary::Torus)
-      return std::string("fingerprint=1 with boundary=") + boundary_name(b) +
-             " on the HIP engine: the fingerprint kernels are compiled for the torus only (the cpu and ref engines "
-             "fingerprint the plane)";
-    if (!rule_is_default(rule))
-      return "fingerprint=1 with rule " + rule_string(rule) +
-             " on the HIP engine: the fingerprint kernels are compiled for B3/S23 only (the cpu and ref engines "
-             "fingerprint under any rule)";
-    if (l == Layout::U8 && tune_.u8_lds)
-      return "fingerprint=1 with u8_kernel=lds: the LDS-tiled byte kernels have no fingerprint";
-    (void)census;
-    return "fingerprint=1 with census=1 on the HIP engine: a temporal block runs one fused per-generation series "
-           "(the cpu and ref engines run both)";
-  }
-  std::string fingerprint_kernel(Layout l) const override { return hipk::life_block_fprint_variant(l, tune_); }
+  std::string feature_kernel(Layout l, BlockMode m) const override { return hipk::life_block_variant(l, tune_, m); }
   KernelChoice choose_conway(Layout l, int64_t rows, int64_t cols, int tmax_req, int xlane) const {
     KernelChoice k{tmax_req > 0 ? tmax_req : preferred_tmax(l), false};
     if (l == Layout::U8 && tmax_req <= 0 && !tune_.u8_lds) {
@@ -1312,6 +1252,46 @@ void Scratch::release() {
 }  // namespace hipk
 
 std::vector<Rule> hip_rules() { return hipk::life_block_rules(); }
+
+// What the HIP engine runs: B3/S23 and the rules of life_rules.def on the
+// torus, none but B3/S23 with the LDS-tiled byte kernels; the plane, the census
+// and the fingerprint each with B3/S23 and without those kernels; the census and
+// the fingerprint on the torus only, and not both.
+std::string hip_refusal(Layout l, Rule rule, Boundary b, BlockFeatures f, bool u8_lds) {
+  const bool lds = l == Layout::U8 && u8_lds, conway = rule_is_default(rule);
+  const std::string bnd = std::string("boundary=") + boundary_name(b), rs = "rule " + rule_string(rule);
+  if (b != Boundary::Torus && lds)
+    return bnd + " with u8_kernel=lds: the LDS-tiled byte kernels wrap their reads around the torus";
+  if (b != Boundary::Torus && !conway)
+    return bnd + " with " + rs + " on the HIP engine: the plane kernels are compiled for B3/S23 only (the cpu and ref "
+           "engines run any rule on the plane)";
+  if (!conway && lds && hipk::life_block_has_rule(rule))
+    return rs + ": the LDS-tiled byte kernels (tuning u8_kernel=lds) run B3/S23 only";
+  if (!hipk::life_block_has_rule(rule)) {
+    std::string have = "B3/S23";
+    for (const Rule r : hipk::life_block_rules()) have += ", " + rule_string(r);
+    return rs + " is not compiled for the HIP engine (compiled: " + have +
+           "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)";
+  }
+  // A series: the temporal-block kernels of either layout, B3/S23 on the torus.
+  const auto series = [&](const std::string& name, const char* verb, const char* on_plane) -> std::string {
+    if (b != Boundary::Torus)
+      return name + "=1 with " + bnd + " on the HIP engine: the " + name +
+             " kernels are compiled for the torus only (the cpu and ref engines " + on_plane + ")";
+    if (!conway)
+      return name + "=1 with " + rs + " on the HIP engine: the " + name +
+             " kernels are compiled for B3/S23 only (the cpu and ref engines " + verb + " under any rule)";
+    if (lds) return name + "=1 with u8_kernel=lds: the LDS-tiled byte kernels have no " + name;
+    return "";
+  };
+  std::string why;
+  if (f.census) why = series("census", "count", "count on the plane");
+  if (why.empty() && f.fingerprint) why = series("fingerprint", "fingerprint", "fingerprint the plane");
+  if (why.empty() && f.fingerprint && f.census)
+    why = "fingerprint=1 with census=1 on the HIP engine: a temporal block runs one fused per-generation series (the "
+          "cpu and ref engines run both)";
+  return why;
+}
 
 bool hip_available() {
   int n = 0;

@@ -84,6 +84,13 @@ const uint8_t* grid_ptr(const py::array_t<uint8_t, py::array::c_style | py::arra
   return a.data();
 }
 
+// Whether the backend runs the combination (Backend::refusal() is empty).
+bool runs(const Backend& b, Layout l, const std::string& rule, const std::string& boundary, bool census = false,
+          bool fingerprint = false) {
+  const Boundary bd = parse_boundary(boundary);
+  return b.refusal(l, parse_rule(rule), bd, {bd == Boundary::Dead, census, fingerprint}).empty();
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_gol, m) {
@@ -169,23 +176,23 @@ PYBIND11_MODULE(_gol, m) {
       .def("device", &Backend::device)
       .def("stream", [](const Backend& b) { return reinterpret_cast<std::uintptr_t>(b.stream()); })
       .def("synchronize", &Backend::synchronize, py::call_guard<py::gil_scoped_release>())
-      .def("supports_rule", [](const Backend& b, Layout l, const std::string& rule) {
-        return b.supports_rule(l, parse_rule(rule));
-      })
+      // Backend::refusal() by the question asked: the named feature with
+      // what else the arguments give; a "dead" boundary implies the plane.
+      .def("supports_rule", [](const Backend& b, Layout l, const std::string& rule) { return runs(b, l, rule, "torus"); })
       .def("supports_boundary", [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary) {
-        return b.supports_boundary(l, parse_rule(rule), parse_boundary(boundary));
+        return runs(b, l, rule, boundary) || boundary == "torus";  // whether it runs the rule: supports_rule
       })
-      .def("plane_kernel", &Backend::plane_kernel)
       .def("supports_census", [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary) {
-        return b.supports_census(l, parse_rule(rule), parse_boundary(boundary));
+        return runs(b, l, rule, boundary, true);
       })
-      .def("census_kernel", &Backend::census_kernel)
       .def("supports_fingerprint",
            [](const Backend& b, Layout l, const std::string& rule, const std::string& boundary, bool census) {
-             return b.supports_fingerprint(l, parse_rule(rule), parse_boundary(boundary), census);
+             return runs(b, l, rule, boundary, census, true);
            },
            py::arg("layout"), py::arg("rule"), py::arg("boundary"), py::arg("census") = false)
-      .def("fingerprint_kernel", &Backend::fingerprint_kernel)
+      .def("plane_kernel", [](const Backend& b, Layout l) { return b.feature_kernel(l, BlockMode::Plane); })
+      .def("census_kernel", [](const Backend& b, Layout l) { return b.feature_kernel(l, BlockMode::Census); })
+      .def("fingerprint_kernel", [](const Backend& b, Layout l) { return b.feature_kernel(l, BlockMode::Fingerprint); })
       .def("bind_thread", &Backend::bind_thread);
   m.def("cpu_backend",
         [](int threads, int drift, std::optional<Tuning> tune) {
@@ -198,6 +205,14 @@ PYBIND11_MODULE(_gol, m) {
         },
         py::arg("device") = 0, py::arg("tune") = py::none());
   m.def("hip_available", &hip_available);
+  // The HIP engine's refusal of a combination ("": it runs), without a device.
+  m.def("hip_refusal",
+        [](Layout l, const std::string& rule, const std::string& boundary, bool census, bool fingerprint, bool u8_lds) {
+          const Boundary b = parse_boundary(boundary);
+          return hip_refusal(l, parse_rule(rule), b, {b == Boundary::Dead, census, fingerprint}, u8_lds);
+        },
+        py::arg("layout"), py::arg("rule"), py::arg("boundary") = "torus", py::arg("census") = false,
+        py::arg("fingerprint") = false, py::arg("u8_lds") = false);
   // Life-like rules (common.hpp): canonical text of a rule given by name or in
   // B/S notation, the named rules, and the rules compiled for the HIP engine.
   m.def("parse_rule", [](const std::string& s) { return rule_string(parse_rule(s)); });

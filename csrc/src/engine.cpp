@@ -40,27 +40,24 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   require_no_b0(cfg_.rule, rule_string(cfg_.rule));
   rank_ = tr_->rank();
   plane_ = cfg_.boundary == Boundary::Dead;
+  const BlockFeatures feat{plane_, cfg_.census, cfg_.fingerprint};
+  census_.on = feat.census;
+  fprint_.on = feat.fingerprint;
+  plain_ = !feat.any();
+  // Combinations a feature is not built for are refused, not run without it.
   if (plane_) {
-    // Combinations that exist on the torus only are refused, not run there.
     GOL_REQUIRE(!cfg_.self_exchange,
                 "boundary=dead with self_exchange (--rehearse-rccl): the rehearsal sends a rank's rows to itself "
                 "around the torus, which the bounded plane does not have");
     GOL_REQUIRE(cfg_.graphs <= 0,
                 "boundary=dead with graphs=1: captured epochs are not built for the bounded plane");
   }
-  if (cfg_.census) {
-    // As for the plane: combinations the census is not built for are refused.
-    GOL_REQUIRE(!cfg_.self_exchange,
-                "census=1 with self_exchange (--rehearse-rccl): the rehearsal's one-rank communicator is not part "
-                "of the census's sum over ranks");
-    GOL_REQUIRE(cfg_.graphs <= 0, "census=1 with graphs=1: captured epochs are not built for the census");
-  }
-  if (cfg_.fingerprint) {
-    // As for the census.
-    GOL_REQUIRE(!cfg_.self_exchange,
-                "fingerprint=1 with self_exchange (--rehearse-rccl): the rehearsal's one-rank communicator is not "
-                "part of the fingerprint's sum over ranks");
-    GOL_REQUIRE(cfg_.graphs <= 0, "fingerprint=1 with graphs=1: captured epochs are not built for the fingerprint");
+  for (const Series* s : {&census_, &fprint_}) {
+    if (!s->on) continue;
+    const std::string n = s->name;
+    GOL_REQUIRE(!cfg_.self_exchange, n + "=1 with self_exchange (--rehearse-rccl): the rehearsal's one-rank communicator "
+                                         "is not part of the " + n + "'s sum over ranks");
+    GOL_REQUIRE(cfg_.graphs <= 0, n + "=1 with graphs=1: captured epochs are not built for the " + n);
   }
   if (cfg_.overlap == 1) cfg_.overlap = 3;  // "on" is the trigger schedule
   int64_t unit = (cfg_.layout == Layout::Bits || cfg_.W % 32 == 0) ? 32 : 1;
@@ -79,14 +76,9 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Layout the temporal blocks run on.
   const Layout cl = via_bits_ ? Layout::Bits : cfg_.layout;
-  if (plane_ && !be_->supports_boundary(cl, cfg_.rule, cfg_.boundary))
-    fail(be_->unsupported_boundary(cl, cfg_.rule, cfg_.boundary));
-  if (!be_->supports_rule(cl, cfg_.rule)) fail(be_->unsupported_rule(cl, cfg_.rule));
-  if (cfg_.census && !be_->supports_census(cl, cfg_.rule, cfg_.boundary))
-    fail(be_->unsupported_census(cl, cfg_.rule, cfg_.boundary));
-  if (cfg_.fingerprint) {
-    if (!be_->supports_fingerprint(cl, cfg_.rule, cfg_.boundary, cfg_.census))
-      fail(be_->unsupported_fingerprint(cl, cfg_.rule, cfg_.boundary, cfg_.census));
+  const std::string refused = be_->refusal(cl, cfg_.rule, cfg_.boundary, feat);
+  if (!refused.empty()) fail(refused);
+  if (feat.fingerprint) {
     // The device kernels weigh whole 32-cell words: every tile must start on
     // the global word grid (the same answer on every rank).
     if (be_->is_device())
@@ -102,8 +94,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // that moves a halo exchange is only consistent in lockstep), so it is
   // made for the smallest tile of the decomposition, not this rank's.
   const Backend::KernelChoice kc =
-      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule,
-                         cfg_.boundary, cfg_.census, cfg_.fingerprint);
+      be_->choose_kernel(cl, min_tile_rows(dec_), std::max<int64_t>(1, min_tile_cols(dec_)), cfg_.tmax, cfg_.rule, feat);
   tmax_ = std::min(kc.tmax, cl == Layout::U8 && !plane_ ? 32 : 16);
   // Epoch depth: a deeper halo means fewer latency-bound exchanges (or local
   // periodic fills: two ~5 us launches each) but ~D redundant rows per epoch.
@@ -194,7 +185,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // Linked launches (Backend::KernelChoice::link): consecutive blocks of an
   // epoch overlap; anything else on the stream (fills, exchanges, polls)
   // joins the streams first.  Not with column fills between blocks.
-  link_ = kc.link && !cols_filled_ && !plane_ && !(cfg_.census || cfg_.fingerprint);
+  link_ = kc.link && !cols_filled_ && plain_;
   // Several ranks: every poll is a flag all-reduce on the compute stream
   // (latency-bound), so poll half as often; a stop is still exact and at most
   // two windows late.
@@ -224,13 +215,12 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // Boundary-triggered sends (overlap = 3; last_block_trigger): row strips
   // on a backend that can count boundary groups done.  Byte tiles on bit
   // words too: the trigger runs on the bit image.
-  // Not on the plane (the trigger rides on linked launches).
-  // Nor with the census (no linked launches).
-  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger() && !plane_ && !(cfg_.census || cfg_.fingerprint);
+  // Plain engines only: the trigger rides on linked launches.
+  const bool trigger_ok = row_exchange && dec_.Px == 1 && be_->supports_trigger() && plain_;
   trigger_ = trigger_ok && cfg_.overlap == 3;
   watchdog_s_ = cfg_.watchdog_s > 0 ? cfg_.watchdog_s : cfg_.tune.f("watchdog_s") > 0 ? cfg_.tune.f("watchdog_s") : 900.0;
   use_graphs_ = cfg_.graphs != 0 && be_->supports_graphs() && tr_->capturable() &&
-                (cfg_.graphs > 0 || tr_->size() == 1) && !plane_ && !(cfg_.census || cfg_.fingerprint);
+                (cfg_.graphs > 0 || tr_->size() == 1) && plain_;
   if (use_graphs_) gen_dev_ = Owned<int64_t>(be_, be_->alloc(sizeof(int64_t)));
   if (use_graphs_) trigger_ = false;  // captured epochs stay on one stream
   // Overlap auto: measure both schedules on the real ranks (see auto_choose);
@@ -272,7 +262,7 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   // a torus that is the same from block to block).  Everything else keeps
   // today's path.
   const Backend::QuietTuning qt = be_->quiet_mode();
-  if (qt.mode != 0 && !plane_ && !(cfg_.census || cfg_.fingerprint) && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
+  if (qt.mode != 0 && plain_ && cl == Layout::Bits && rule_is_default(cfg_.rule) && rows_ring_ && !cols_filled_ &&
       tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_ && tmax_ == be_->quiet_block() && D_ == tmax_) {
     quiet_.mode = qt.mode;
     quiet_.scout = qt.scout;
@@ -282,7 +272,8 @@ Engine::Engine(const EngineConfig& cfg, Backend* backend, Transport* transport)
   }
   // Lazy tail (run_impl): single-rank ring tiles whose epochs are one block.
   tail_mode_ = cfg_.tune.i("lazy_tail");
-  tail_ok_ = tail_mode_ != 0 && !plane_ && !(cfg_.census || cfg_.fingerprint) && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange && !use_graphs_;
+  tail_ok_ = tail_mode_ != 0 && plain_ && rows_ring_ && D_ == tmax_ && tr_->size() == 1 && !cfg_.self_exchange &&
+             !use_graphs_;
   if (tail_ok_) carry_ = Owned<uint32_t>(be_, be_->alloc(size_t(tmax_) * 4));
   gen_ = cfg_.start_gen;
 }
@@ -895,20 +886,17 @@ int Engine::launch(void* in, void* out, const TileGeom& g, int T, int64_t row_lo
                     : nullptr;
   }
   a.flags_base = flags_base_;
-  if (census_run_) {
-    // Every block of a census run lies in the window and records: a block
+  for (const Series* s : {&census_, &fprint_}) {
+    if (!s->run) continue;
+    // Every block of a series' run lies in the window and records: a block
     // without flags (a lazy tail's replay) or beyond the window would lose or
-    // double a generation of the series.  Census engines run no lazy tail and
-    // no graphs, so neither arises.
+    // double a generation of the series.  Its engines run no lazy tail and no
+    // graphs, so neither arises.
     GOL_REQUIRE(!no_flags_ && !capturing_ && gen_base >= flags_base_ && gen_base + T < flags_base_ + flags_len_,
-                "census: a temporal block outside the run's window");
-    a.census = census_.get();
+                std::string(s->name) + ": a temporal block outside the run's window");
+    (s == &census_ ? a.census : a.fingerprint) = s->win.get();
   }
-  if (fprint_run_) {
-    // As for the census.
-    GOL_REQUIRE(!no_flags_ && !capturing_ && gen_base >= flags_base_ && gen_base + T < flags_base_ + flags_len_,
-                "fingerprint: a temporal block outside the run's window");
-    a.fingerprint = fprint_.get();
+  if (fprint_.run) {
     a.global_row0 = rows().begin;
     a.global_col0 = cols().begin;
   }
@@ -1128,30 +1116,22 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
     flags_len_ = std::max<int64_t>(need, 64);
     flags_ = Owned<uint32_t>(be_, be_->alloc(size_t(flags_len_) * 4));
     flags_host_ = Owned<uint32_t>(be_, be_->alloc_host(size_t(flags_len_) * 4), /*host=*/true);
-    if (cfg_.census) {
-      census_.reset();
-      census_ = Owned<uint64_t>(be_, be_->alloc(size_t(flags_len_) * 8));
-    }
-    fprint_.reset();  // below: its length is the flags'
+    for (Series* s : {&census_, &fprint_}) s->win.reset();  // below: their length is the flags'
   }
-  if (cfg_.fingerprint && !fprint_) fprint_ = Owned<uint64_t>(be_, be_->alloc(size_t(flags_len_) * 8));
   flags_base_ = start;
   be_->memset_async(flags_, 0, size_t(flags_len_) * 4);
-  if (cfg_.census) {
-    GOL_REQUIRE(ahead_ == 0, "census: a lazy tail is pending");
-    be_->memset_async(census_, 0, size_t(flags_len_) * 8);
+  GOL_REQUIRE(!census_.on || ahead_ == 0, "census: a lazy tail is pending");
+  GOL_REQUIRE(!fprint_.on || (ahead_ == 0 && drift_ == 0), "fingerprint: a lazy tail or a drifted frame is pending");
+  struct SeriesRunEnd {  // also when the run throws
+    Engine* e;
+    ~SeriesRunEnd() { e->census_.run = e->fprint_.run = false; }
+  } series_run_end{this};
+  for (Series* s : {&census_, &fprint_}) {
+    if (!s->on) continue;
+    if (!s->win) s->win = Owned<uint64_t>(be_, be_->alloc(size_t(flags_len_) * 8));
+    be_->memset_async(s->win, 0, size_t(flags_len_) * 8);
+    s->run = true;
   }
-  census_run_ = cfg_.census;
-  struct CensusRunEnd {  // also when the run throws
-    bool& on;
-    ~CensusRunEnd() { on = false; }
-  } census_run_end{census_run_};
-  if (cfg_.fingerprint) {
-    GOL_REQUIRE(ahead_ == 0 && drift_ == 0, "fingerprint: a lazy tail or a drifted frame is pending");
-    be_->memset_async(fprint_, 0, size_t(flags_len_) * 8);
-  }
-  fprint_run_ = cfg_.fingerprint;
-  CensusRunEnd fprint_run_end{fprint_run_};
   if (carried > 0)
     be_->copy_2d_async(flags_ + flag_offset(start), carried * 4, carry_.get(), carried * 4, carried * 4, 1);
   if (use_graphs_) {
@@ -1251,8 +1231,7 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
     }
   }
   if (have_pending) poll_check(pending, &found);
-  census_run_ = false;
-  fprint_run_ = false;
+  census_.run = fprint_.run = false;
   if (via_bits_) bits_live_ = true;  // unpacked when the byte tile is next read (sync_bytes)
   // A poll issued just before an early stop may still run on the side stream
   // (the final alive reduction below uses the same communicator, and the
@@ -1279,31 +1258,22 @@ RunResult Engine::run_impl(int64_t limit, bool stop_early) {
   res.linked_launches = be_->linked_launches() - lk0;
   res.generations = limit;
   collect_phases(res);
-  if (cfg_.census) {
-    // The series of (start, gen_]: summed over ranks and copied once per run.
-    // (A stop leaves gen_ at the last generation evaluated, and every
-    // generation up to it was counted.)
+  // A series of (start, gen_]: summed over ranks (a fingerprint's shares add up
+  // modulo 2^64) and copied once per run into its 64-bit entries.  (A stop
+  // leaves gen_ at the last generation evaluated, and every generation up to
+  // it was recorded.)
+  const auto collect = [&](const Series& s, auto& out) {
     const int64_t n = gen_ - start;
-    std::vector<uint64_t> counts(static_cast<size_t>(n));
-    if (n > 0) {
-      uint64_t* dev = census_ + flag_offset(start);
-      if (tr_->size() > 1) tr_->allreduce_sum_u64(dev, size_t(n), be_->stream());
-      be_->synchronize();
-      be_->copy_d2h(counts.data(), dev, size_t(n) * 8);
-    }
-    res.population.assign(counts.begin(), counts.end());
-  }
-  if (cfg_.fingerprint) {
-    // Likewise; the ranks' shares add up modulo 2^64.
-    const int64_t n = gen_ - start;
-    res.fingerprint.resize(static_cast<size_t>(n));
-    if (n > 0) {
-      uint64_t* dev = fprint_ + flag_offset(start);
-      if (tr_->size() > 1) tr_->allreduce_sum_u64(dev, size_t(n), be_->stream());
-      be_->synchronize();
-      be_->copy_d2h(res.fingerprint.data(), dev, size_t(n) * 8);
-    }
-  }
+    if (!s.on) return;
+    out.resize(static_cast<size_t>(n));
+    if (n <= 0) return;
+    uint64_t* dev = s.win + flag_offset(start);
+    if (tr_->size() > 1) tr_->allreduce_sum_u64(dev, size_t(n), be_->stream());
+    be_->synchronize();
+    be_->copy_d2h(out.data(), dev, size_t(n) * 8);
+  };
+  collect(census_, res.population);
+  collect(fprint_, res.fingerprint);
   if (found >= 0) {
     res.first_unchanged = found;
     const Tile s = state_tile();

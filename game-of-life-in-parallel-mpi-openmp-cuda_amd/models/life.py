@@ -422,28 +422,23 @@ class Simulation:
             parts.append("row ring (no halo fills)")
         if e.config.rule != DEFAULT_RULE:
             parts.append(f"rule {e.config.rule}")
-        if e.config.boundary != DEFAULT_BOUNDARY:
-            # The plane's kernels: the DPP window whatever xlane asks for, T <= 16 in both layouts.
-            parts.append(f"boundary {e.config.boundary} (bounded plane: edge masked in the temporal blocks, T <= 16)")
-            pk = self.backend.plane_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
-            if pk:
-                parts.append(f"plane kernels: {pk}")
-        if e.config.census:
-            # The census kernels: the DPP window whatever xlane asks for, T <= 16 in both layouts;
-            # the row ring and wrapped column reads stay (their blocks cover the owned cells once).
-            parts.append("census (per-generation live-cell counts fused into the temporal blocks; no linked or "
-                         "chained launches, no skipping, no lazy tail, no folded strip)")
-            ck = self.backend.census_kernel(native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8)
-            if ck:
-                parts.append(f"census kernels: {ck}")
-        if e.config.fingerprint:
-            # The fingerprint kernels: scheduled like the census kernels.
-            parts.append("fingerprint (per-generation 64-bit grid fingerprints fused into the temporal blocks; no "
-                         "linked or chained launches, no skipping, no lazy tail, no folded strip)")
-            fk = self.backend.fingerprint_kernel(native().Layout.Bits if lay == "bits" or e.via_bits
-                                                 else native().Layout.U8)
-            if fk:
-                parts.append(f"fingerprint kernels: {fk}")
+        # The feature kernels: the DPP window whatever xlane asks for, T <= 16 in both layouts; a
+        # series keeps the row ring and wrapped column reads (its blocks cover the owned cells once).
+        series = ("fused into the temporal blocks; no linked or chained launches, no skipping, no lazy tail, "
+                  "no folded strip")
+        compute = native().Layout.Bits if lay == "bits" or e.via_bits else native().Layout.U8
+        for on, phrase, kernel, label in (
+                (e.config.boundary != DEFAULT_BOUNDARY,
+                 f"boundary {e.config.boundary} (bounded plane: edge masked in the temporal blocks, T <= 16)",
+                 self.backend.plane_kernel, "plane"),
+                (e.config.census, f"census (per-generation live-cell counts {series})",
+                 self.backend.census_kernel, "census"),
+                (e.config.fingerprint, f"fingerprint (per-generation 64-bit grid fingerprints {series})",
+                 self.backend.fingerprint_kernel, "fingerprint")):
+            if on:
+                parts.append(phrase)
+                if kernel(compute):
+                    parts.append(f"{label} kernels: {kernel(compute)}")
         return ", ".join(parts)
 
     # -- state -----------------------------------------------------------
