@@ -40,14 +40,12 @@
 #include "gol/backend.hpp"
 #include "gol/batch.hpp"
 #include "gol/hip_util.hpp"
+#include "life_batch_common.hpp"
 #include "life_block_impl.hpp"
 
 namespace gol {
 namespace hipk {
 namespace batch {
-
-constexpr int kBlock = 256;  // four independent waves per workgroup
-constexpr int kVmDpp = 0, kVmBpermute = 1;
 
 struct Args {
   int64_t B;
@@ -66,23 +64,6 @@ struct Args {
   uint32_t K;
   uint32_t share;
 };
-
-// Lane i receives v of the lane one row above (kUp) or below within its
-// universe of H lanes, wrapping inside the universe.  Every lane of a rotate
-// has a source, so bound_ctrl changes no value: it only spares the move that
-// would initialise the destination.
-template <int H, int VM, bool kUp>
-__device__ __forceinline__ uint32_t vmove(uint32_t v, int src4) {
-  if constexpr (VM == kVmDpp && H == 64) {
-    constexpr int ctrl = kUp ? 0x13C : 0x134;  // wave_ror:1 : wave_rol:1
-    return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), ctrl, 0xF, 0xF, true));
-  } else if constexpr (VM == kVmDpp && H == 16) {
-    constexpr int ctrl = kUp ? 0x121 : 0x12F;  // row_ror:1 : row_ror:15
-    return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), ctrl, 0xF, 0xF, true));
-  } else {
-    return uint32_t(__builtin_amdgcn_ds_bpermute(src4, int(v)));
-  }
-}
 
 // ---- rule policies ------------------------------------------------------------
 // State: what a lane keeps of its universe's rule over the loop.  soup(): the
@@ -171,16 +152,7 @@ __global__ __launch_bounds__(kBlock) void life_batch_kernel(const Args a) {
     const int64_t soup = Rule::soup(a, u);
     if (a.cells) {
       const uint32_t* src = reinterpret_cast<const uint32_t*>(a.cells + (soup * H + row) * int64_t(32 * NW));
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const uint32_t v = src[8 * i + q];  // four cells, one per byte
-          w |= ((v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u)) << (4 * q);
-        }
-        c[i] = w;
-      }
+      GOL_BATCH_PACK_ROW(NW, src, c)
     } else {
       const uint64_t seed = a.seed + uint64_t(soup);
 #pragma unroll
@@ -279,9 +251,6 @@ struct RuleTable {
   LaunchFn fn[2][4][2][2];
 };
 
-// Whether the height has a DPP move of its own (the others always permute).
-constexpr bool has_dpp(int H) { return H == 64 || H == 16; }
-
 template <class R, int NW, int H>
 void fill_shape(LaunchFn (&f)[2][2]) {
   constexpr int kDpp = has_dpp(H) ? kVmDpp : kVmBpermute;
@@ -322,19 +291,6 @@ const RuleTable& word_table() {
   return t;
 }
 
-template <class T>
-struct DeviceBuf {
-  T* p = nullptr;
-  explicit DeviceBuf(size_t n) {
-    if (n) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
-  }
-  ~DeviceBuf() {
-    if (p) (void)hipFree(p);
-  }
-  DeviceBuf(const DeviceBuf&) = delete;
-  DeviceBuf& operator=(const DeviceBuf&) = delete;
-};
-
 }  // namespace batch
 }  // namespace hipk
 
@@ -351,12 +307,7 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
     fail("rule " + rule_string(cfg.rule) + " is not compiled for the HIP engine (compiled: B3/S23, " + have +
          "; add a line to csrc/kernels/life_rules.def, or run it on the CPU engine)");
   }
-  const std::string& vm_text = tune.s("batch_vmove");
-  GOL_REQUIRE(vm_text == "auto" || vm_text == "dpp" || vm_text == "bpermute",
-              "tuning batch_vmove=" + vm_text + ": auto, dpp or bpermute");
-  GOL_REQUIRE(vm_text != "dpp" || hb::has_dpp(cfg.H),
-              "tuning batch_vmove=dpp: heights 64 and 16 have a DPP move, " + std::to_string(cfg.H) + " permutes");
-  const int vm = vm_text == "bpermute" || !hb::has_dpp(cfg.H) ? hb::kVmBpermute : hb::kVmDpp;
+  const int vm = hb::parse_vmove(tune, cfg.H);
   GOL_REQUIRE(hip_available(), "no HIP device available (HIP engine requested)");
 
   const int W = cfg.W, H = cfg.H, NW = W / 32, upw = 64 / H;
@@ -372,7 +323,8 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   const size_t nb = size_t(B);
   hb::DeviceBuf<int32_t> d_gens(nb), d_per(nb), d_pop(nb);
   hb::DeviceBuf<uint8_t> d_stop(nb);
-  hb::DeviceBuf<uint32_t> d_words(cfg.want_grids ? size_t(B) * H * NW : 0);
+  // The cluster census reads the final words on the device.
+  hb::DeviceBuf<uint32_t> d_words(cfg.want_grids || cfg.clusters ? size_t(B) * H * NW : 0);
   if (in.cells) HIP_CHECK(hipMemcpy(d_cells.p, in.cells, n_cells, hipMemcpyHostToDevice));
   if (by_word) {
     std::vector<uint32_t> words(cfg.rules.size());
@@ -396,23 +348,8 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   a.K = uint32_t(by_word ? cfg.soups_per_rule : 1);
   a.share = cfg.share_soups ? 1u : 0u;
 
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
   BatchResult res;
-  float ms = 0;
-  hipError_t err = hipEventRecord(e0, nullptr);
-  if (err == hipSuccess) {
-    fn(a, waves, nullptr);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipEventRecord(e1, nullptr);
-  if (err == hipSuccess) err = hipEventSynchronize(e1);
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  HIP_CHECK(err);
-  res.kernel_ms = ms;
+  res.kernel_ms = hb::timed_launch([&] { fn(a, waves, nullptr); });
 
   res.generations.resize(size_t(B));
   res.period.resize(size_t(B));
@@ -432,6 +369,7 @@ BatchResult run_batch_hip(int device, const BatchConfig& cfg, const BatchInput& 
   const char* move = vm == hb::kVmBpermute ? "ds_bpermute" : H == 64 ? "dpp wave_ror/rol" : "dpp row_ror";
   res.variant = "batch " + std::to_string(W) + "x" + std::to_string(H) + " " + boundary_name(cfg.boundary) + " " +
                 std::to_string(upw) + "/wave " + move + " " + batch_rule_text(cfg);
+  if (cfg.clusters) res.census = hb::find_clusters_device(W, H, dead, vm, B, nullptr, d_words.p);
   return res;
 }
 

@@ -121,6 +121,7 @@ BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput&
   res.population.assign(size_t(B), 0);
   res.stop.assign(size_t(B), 0);
   if (cfg.want_grids) res.grids.assign(size_t(B * H * W), 0);
+  std::vector<uint64_t> final_rows(cfg.clusters ? size_t(B * H) : 0);  // what the cluster census reads
   const uint32_t th = density_thresh(in.density);
   const auto body = [&](int64_t b0, int64_t b1) {
     uint64_t rows[64];
@@ -145,6 +146,8 @@ BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput&
       if (cfg.want_grids)
         for (int y = 0; y < H; ++y)
           for (int x = 0; x < W; ++x) res.grids[size_t((b * H + y) * W + x)] = uint8_t((rows[y] >> x) & 1u);
+      if (cfg.clusters)
+        for (int y = 0; y < H; ++y) final_rows[size_t(b * H + y)] = rows[y];
     }
   };
   const auto t0 = std::chrono::steady_clock::now();
@@ -157,6 +160,7 @@ BatchResult run_batch_cpu(int threads, const BatchConfig& cfg, const BatchInput&
   res.kernel_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   res.variant = "batch cpu " + std::to_string(W) + "x" + std::to_string(H) + " " + boundary_name(cfg.boundary) +
                 " rows64 " + batch_rule_text(cfg);
+  if (cfg.clusters) res.census = find_clusters_rows(threads, W, H, cfg.boundary, B, final_rows.data());
   return res;
 }
 

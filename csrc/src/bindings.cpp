@@ -93,6 +93,18 @@ bool runs(const Backend& b, Layout l, const std::string& rule, const std::string
 
 }  // namespace
 
+// ClusterCensus as NumPy arrays: (clusters, universe, signature, cells, height, width, spanning, ms, count_ms).
+template <class T>
+py::array_t<T> copy_array(const std::vector<T>& v) {
+  py::array_t<T> a(static_cast<py::ssize_t>(v.size()));
+  std::copy(v.begin(), v.end(), a.mutable_data());
+  return a;
+}
+py::tuple census_arrays(const ClusterCensus& c) {
+  return py::make_tuple(copy_array(c.clusters), copy_array(c.universe), copy_array(c.signature), copy_array(c.cells),
+                        copy_array(c.height), copy_array(c.width), copy_array(c.spanning), c.ms, c.count_ms);
+}
+
 PYBIND11_MODULE(_gol, m) {
   m.doc() = "gol-mi355x native engine (CDNA4 HIP kernels, RCCL halos, C++ runtime)";
   py::register_exception<Error>(m, "GolError", PyExc_RuntimeError);
@@ -671,8 +683,9 @@ PYBIND11_MODULE(_gol, m) {
            int W, int H, uint64_t seed, double density, int64_t max_gens, int64_t max_period,
            const std::string& rule, const std::string& boundary, const std::string& engine, bool return_grids,
            int threads, int device, std::optional<Tuning> tune, const std::vector<std::string>& rules,
-           int64_t soups, bool share_soups) -> py::tuple {
+           int64_t soups, bool share_soups, bool clusters) -> py::tuple {
           BatchConfig cfg;
+          cfg.clusters = clusters;
           BatchInput in;
           for (size_t r = 0; r < rules.size(); ++r) {
             try {
@@ -725,6 +738,8 @@ PYBIND11_MODULE(_gol, m) {
             cells = py::array_t<uint8_t>({int64_t(B), int64_t(H), int64_t(W)},
                                          {int64_t(H) * W, int64_t(W), int64_t(1)}, heap->data(), owner);
           }
+          if (clusters)
+            return py::make_tuple(gens, per, stop, pop, cells, r.kernel_ms, r.variant, census_arrays(r.census));
           return py::make_tuple(gens, per, stop, pop, cells, r.kernel_ms, r.variant);
         },
         py::arg("grids") = py::none(), py::arg("batch") = 0, py::arg("W") = 64, py::arg("H") = 64,
@@ -732,7 +747,42 @@ PYBIND11_MODULE(_gol, m) {
         py::arg("rule") = "B3/S23", py::arg("boundary") = "torus", py::arg("engine") = "cpu",
         py::arg("return_grids") = false, py::arg("threads") = 0, py::arg("device") = 0,
         py::arg("tune") = py::none(), py::arg("rules") = std::vector<std::string>{}, py::arg("soups") = 1,
-        py::arg("share_soups") = false);
+        py::arg("share_soups") = false, py::arg("clusters") = false);
+
+  // The cluster census of arbitrary grids (B, H, W) of a batch shape: (clusters per universe, universe,
+  // signature, cells, height, width, spanning, ms, count_ms).
+  m.def("find_clusters",
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> grids, const std::string& boundary,
+           const std::string& engine, int threads, int device, std::optional<Tuning> tune) -> py::tuple {
+          GOL_REQUIRE(grids.ndim() == 3, "find_clusters: the grids are a (B, H, W) uint8 array, got " +
+                                             std::to_string(grids.ndim()) + " dimensions");
+          GOL_REQUIRE(engine == "cpu" || engine == "hip", "find_clusters: engine '" + engine + "': cpu or hip");
+          const int64_t B = grids.shape(0);
+          const int H = int(std::min<int64_t>(grids.shape(1), 1 << 20)), W = int(std::min<int64_t>(grids.shape(2), 1 << 20));
+          const Boundary bd = parse_boundary(boundary);
+          const uint8_t* cells = grids.data();
+          ClusterCensus c;
+          {
+            py::gil_scoped_release rel;
+            c = engine == "hip" ? find_clusters_hip(device, W, H, bd, B, cells, tune ? *tune : Tuning::from_env())
+                                : find_clusters_cpu(threads, W, H, bd, B, cells);
+          }
+          return census_arrays(c);
+        },
+        py::arg("grids"), py::arg("boundary") = "torus", py::arg("engine") = "cpu", py::arg("threads") = 0,
+        py::arg("device") = 0, py::arg("tune") = py::none());
+  m.def("cluster_signature", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> cells) {
+    GOL_REQUIRE(cells.ndim() == 2, "cluster_signature: expected a 2-D array");
+    return cluster_signature(cells.data(), cells.shape(1), cells.shape(0));
+  });
+  m.def("cluster_name", &cluster_name);
+  // The exclusive scan every engine applies to the per-universe counts (refuses more than 2^28 records).
+  m.def("cluster_offsets", [](const std::vector<int32_t>& counts) {
+    std::vector<int32_t> offsets;
+    const int64_t total = cluster_offsets(counts, offsets);
+    return py::make_tuple(total, offsets);
+  });
+  m.attr("CLUSTER_RECORDS_MAX") = kClusterRecordsMax;
 
   // ---- serial reference (src/game.c semantics) ----
   m.def("cpu_reference_run",

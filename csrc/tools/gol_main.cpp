@@ -117,6 +117,7 @@ struct Options {
   int64_t batch = 0;            // --batch N (0: off)
   int64_t max_period = 64;      // --max-period P
   std::string batch_csv;        // --batch-csv PATH
+  std::string batch_census;     // --batch-census PATH: the cluster census of the final grids
   // A rule per universe: --batch-rules FILE|all, R rules.  Without --soups
   // universe b runs rule b on the soup of seed SEED + b; with --soups K
   // universe r*K + j runs rule r on the soup of seed SEED + j.
@@ -286,6 +287,9 @@ void write_window(const Options::Window& w, const std::vector<uint8_t>& cells, R
                "  --max-period P              --batch: the largest period recognised, 1 to 65536 (default 64)\n"
                "  --batch-csv PATH            --batch: write 'universe,seed,generations,stop,period,population'\n"
                "                              lines, one per universe (stop: limit, cycle or extinction)\n"
+               "  --batch-census PATH         --batch: find the clusters of every final grid (live cells at most 2\n"
+               "                              cells apart) and write 'signature,name,cells,height,width,spanning,\n"
+               "                              count', one line per kind of cluster, the most common first\n"
                "  --batch-rules FILE|all      --batch with a rule per universe, N = the number of rules R (an explicit\n"
                "                              --batch N must agree): FILE holds one rule per line (# comments and\n"
                "                              blank lines skipped), all = the 131072 Life-like rules without B0;\n"
@@ -323,6 +327,7 @@ Options parse(int argc, char** argv) {
       if (o.batch < 1) throw Error("--batch: the number of universes must be at least 1");
     } else if (a == "--max-period") o.max_period = std::atoll(next().c_str());
     else if (a == "--batch-csv") o.batch_csv = next();
+    else if (a == "--batch-census") o.batch_census = next();
     else if (a == "--batch-rules") o.batch_rules = next();
     else if (a == "--rules-csv") o.rules_csv = next();
     else if (a == "--soups") {
@@ -444,6 +449,7 @@ Options parse(int argc, char** argv) {
     return o;
   }
   if (o.max_period != 64 || !o.batch_csv.empty()) throw Error("--max-period and --batch-csv need --batch N");
+  if (!o.batch_census.empty()) throw Error("--batch-census needs --batch N or --batch-rules FILE|all");
   if (!o.resume.empty()) {
     // The checkpoint fixes the grid and the counters; --gens / --sim-freq /
     // --no-similarity given on the command line still win.
@@ -565,6 +571,7 @@ int run_batch(const Options& o) {
   cfg.boundary = o.boundary;
   cfg.max_gens = o.gens;
   cfg.max_period = o.max_period;
+  cfg.clusters = !o.batch_census.empty();
   BatchInput in;
   in.B = o.batch;
   const bool by_rule = !o.batch_rules.empty();
@@ -617,6 +624,19 @@ int run_batch(const Options& o) {
       f << line;
     }
   }
+  std::vector<ClusterKind> kinds;
+  if (cfg.clusters) {
+    kinds = cluster_table(r.census);
+    std::ofstream f(o.batch_census);
+    GOL_REQUIRE(f.good(), "--batch-census: cannot write '" + o.batch_census + "'");
+    f << "signature,name,cells,height,width,spanning,count\n";
+    for (const ClusterKind& k : kinds) {
+      char sig[17];
+      std::snprintf(sig, sizeof sig, "%016llx", (unsigned long long)k.signature);
+      f << sig << "," << cluster_name(k.signature) << "," << k.cells << "," << k.height << "," << k.width << ","
+        << int(k.spanning) << "," << k.count << "\n";
+    }
+  }
   if (!o.metrics.empty()) {
     std::ofstream f(o.metrics);
     f << "{\"engine\": " << jstr(engine) << ", \"rule\": " << jstr(rule_string(o.rule))
@@ -627,11 +647,21 @@ int run_batch(const Options& o) {
       << ", \"limit\": " << counts[0] << ", \"cycle\": " << counts[1] << ", \"extinction\": " << counts[2]
       << ", \"max_generations\": " << longest;
     if (by_rule) f << ", \"batch_rules\": " << cfg.rules.size() << ", \"batch_soups\": " << K;
+    if (cfg.clusters)
+      f << ", \"batch_clusters\": " << r.census.size() << ", \"batch_cluster_kinds\": " << kinds.size()
+        << ", \"batch_clusters_ms\": " << r.census.ms;
     f << "}\n";
   }
   std::printf("Batch: %lld universes: %lld limit, %lld cycle, %lld extinction; largest generations %d\n",
               (long long)in.B, (long long)counts[0], (long long)counts[1], (long long)counts[2], int(longest));
   if (by_rule) std::printf("Rules: %lld rules x %lld soups\n", (long long)cfg.rules.size(), (long long)K);
+  if (cfg.clusters) {
+    std::printf("Clusters: %lld in %lld universes, %lld kinds", (long long)r.census.size(), (long long)in.B,
+                (long long)kinds.size());
+    if (!kinds.empty())
+      std::printf("; most common %s x%lld", cluster_name(kinds[0].signature).c_str(), (long long)kinds[0].count);
+    std::printf("\n");
+  }
   std::fflush(stdout);
   return 0;
 }

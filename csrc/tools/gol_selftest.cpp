@@ -216,10 +216,28 @@ bool batch_case() {
     cfg.max_gens = max_gens;
     cfg.max_period = P;
     cfg.want_grids = true;
+    cfg.clusters = true;
     BatchInput in;
     in.B = B;
     in.cells = cells.data();
     const BatchResult r = run_batch_cpu(3, cfg, in);
+    // The cluster census of the run against the finder on its final grids and
+    // on the start grids: the counts add up, every cell is in one cluster.
+    const std::vector<uint8_t>* const both[] = {&r.grids, &cells};
+    for (const std::vector<uint8_t>* grids : both) {
+      const ClusterCensus c = find_clusters_cpu(2, W, H, bd, B, grids->data());
+      int64_t records = 0, in_clusters = 0, live = 0;
+      for (const int32_t n : c.clusters) records += n;
+      for (const int32_t n : c.cells) in_clusters += n;
+      for (const uint8_t v : *grids) live += v;
+      bool same = records == int64_t(c.size()) && in_clusters == live;
+      if (grids == &r.grids)
+        same = same && c.clusters == r.census.clusters && c.signature == r.census.signature &&
+               c.universe == r.census.universe && c.cells == r.census.cells && c.height == r.census.height &&
+               c.width == r.census.width && c.spanning == r.census.spanning;
+      if (!same) std::printf("  batch clusters (%s): census mismatch\n", boundary_name(bd));
+      ok = ok && same;
+    }
     for (int64_t b = 0; b < B; ++b) {
       std::vector<uint8_t> g(cells.begin() + b * W * H, cells.begin() + (b + 1) * W * H), snap = g, nxt(g.size());
       int32_t gens = int32_t(max_gens), period = 0;
@@ -258,6 +276,15 @@ bool batch_case() {
       ok = ok && same;
     }
   }
+  const uint8_t block[4] = {1, 1, 1, 1}, two[5] = {1, 0, 0, 0, 1};
+  bool named = cluster_name(cluster_signature(block, 2, 2)) == "block";
+  try {
+    (void)cluster_signature(two, 5, 1);
+    named = false;
+  } catch (const Error&) {
+  }
+  if (!named) std::printf("  batch clusters: the block's name, or two clusters taken for one\n");
+  ok = ok && named;
   std::printf("batch cpu 32x8, 6 universes, torus and dead -> %s\n", ok ? "ok" : "MISMATCH");
   return ok;
 }

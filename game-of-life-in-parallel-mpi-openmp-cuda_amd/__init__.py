@@ -12,7 +12,8 @@ Import as ``gol_amd`` (symlink to this directory).
 from ._native import hip_available, native
 from .models.life import (CycleReport, LifeConfig, RunReport, Simulation, density_image, grid_fingerprint, make_backend,
                           parse_rule, read_rle, reference_run, simulate, write_pgm, write_rle)
-from .models.batch import BATCH_STOP, BatchResult, life_like_rules, simulate_batch
+from .models.batch import (BATCH_STOP, CLUSTER_RECORD, BatchResult, cluster_name, cluster_signature, cluster_table,
+                           find_clusters, life_like_rules, simulate_batch)
 from .ops.life_ops import life_step, life_step_numpy, life_step_torch, random_grid
 
 __version__ = "0.1.0"
@@ -31,4 +32,5 @@ def __getattr__(name):
 __all__ = ["CycleReport", "grid_fingerprint", "LifeConfig", "RunReport", "Simulation", "make_backend", "reference_run", "simulate",
            "life_step", "life_step_numpy", "life_step_torch", "random_grid", "native",
            "hip_available", "parse_rule", "RULES", "read_rle", "write_rle", "density_image", "write_pgm", "BATCH_STOP", "BatchResult",
-           "simulate_batch", "life_like_rules", "__version__"]
+           "simulate_batch", "life_like_rules", "find_clusters", "cluster_signature", "cluster_name", "cluster_table",
+           "CLUSTER_RECORD", "__version__"]

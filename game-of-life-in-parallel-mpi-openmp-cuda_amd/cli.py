@@ -101,6 +101,10 @@ def parse_args(argv=None):
                    help="--batch: the largest period recognised, 1 to 65536 (default 64)")
     p.add_argument("--batch-csv", default=None, metavar="PATH",
                    help="--batch: write 'universe,seed,generations,stop,period,population' lines, one per universe")
+    p.add_argument("--batch-census", default=None, metavar="PATH",
+                   help="--batch: find the clusters of every final grid (live cells at most 2 cells apart) and write "
+                        "'signature,name,cells,height,width,spanning,count', one line per kind of cluster, the most "
+                        "common first")
     p.add_argument("--batch-rules", default=None, metavar="FILE|all",
                    help="--batch with a rule per universe, N = the number of rules R (an explicit --batch N must "
                         "agree): FILE holds one rule per line (# comments and blank lines skipped), all = the 131072 "
@@ -308,7 +312,7 @@ def run_batch(a) -> int:
                            max_period=64 if a.max_period is None else a.max_period,
                            rule=a.rule if a.rule is not None else DEFAULT_RULE,
                            boundary=a.boundary or DEFAULT_BOUNDARY, engine=a.engine, threads=a.threads,
-                           tune=parse_tune_args(a.tune))
+                           tune=parse_tune_args(a.tune), clusters=a.batch_census is not None)
     except RuntimeError as e:
         raise SystemExit(f"gol: error: {e}")
     names = r.stop_names()
@@ -330,16 +334,28 @@ def run_batch(a) -> int:
                         f"{per['mean_population'][i]:.6f}\n")
     counts = r.counts()
     longest = int(r.generations.max())
+    census = {}
+    if a.batch_census is not None:
+        kinds = r.cluster_table()
+        with open(a.batch_census, "w") as f:
+            f.write("signature,name,cells,height,width,spanning,count\n")
+            for sig, name, cells, height, width, spanning, count in kinds:
+                f.write(f"{sig:016x},{name},{cells},{height},{width},{spanning},{count}\n")
+        census = {"batch_clusters": len(r.cluster_records), "batch_cluster_kinds": len(kinds),
+                  "batch_clusters_ms": r.clusters_ms}
     write_json(a.metrics_json, {"engine": "cpu" if r.variant.startswith("batch cpu") else "hip", "rule": parse_rule(a.rule) if a.rule is not None else DEFAULT_RULE,
                                 "boundary": a.boundary or DEFAULT_BOUNDARY, "width": a.width, "height": a.height,
                                 "batch": a.batch, "seed": seed, "density": density, "max_gens": a.gens,
                                 "max_period": 64 if a.max_period is None else a.max_period,
                                 "batch_kernel_ms": r.kernel_ms, "batch_variant": r.variant, **counts,
                                 "max_generations": longest,
-                                **({"batch_rules": len(rules), "batch_soups": K} if rules else {})})
+                                **({"batch_rules": len(rules), "batch_soups": K} if rules else {}), **census})
     sys.stdout.write(batch_summary(a.batch, counts, longest))
     if rules:
         sys.stdout.write(f"Rules: {len(rules)} rules x {K} soups\n")
+    if a.batch_census is not None:
+        most = f"; most common {kinds[0][1]} x{kinds[0][6]}" if kinds else ""
+        sys.stdout.write(f"Clusters: {len(r.cluster_records)} in {a.batch} universes, {len(kinds)} kinds{most}\n")
     sys.stdout.flush()
     return 0
 
@@ -355,6 +371,8 @@ def main(argv=None) -> int:
         return run_batch(a)
     if a.max_period is not None or a.batch_csv is not None:
         raise SystemExit("--max-period and --batch-csv need --batch N")
+    if a.batch_census is not None:
+        raise SystemExit("--batch-census needs --batch N or --batch-rules FILE|all")
     if a.input_file is None and a.random is None and a.resume is None:
         print("Finished")
         return 0

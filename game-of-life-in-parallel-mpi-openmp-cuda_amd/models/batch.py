@@ -19,6 +19,75 @@ from .life import DEFAULT_BOUNDARY, DEFAULT_RULE, make_tuning, parse_rule
 # Names of the ``BatchResult.stop`` codes.
 BATCH_STOP = ("limit", "cycle", "extinction")
 
+# A cluster record (csrc/include/gol/batch.hpp): ``height`` and ``width`` are
+# the extents in rows and columns, ``spanning`` is ``SPANS_X`` (the cluster
+# goes round the torus' columns) | ``SPANS_Y`` (round its rows).
+CLUSTER_RECORD = np.dtype([("universe", np.int32), ("signature", np.uint64), ("cells", np.int32),
+                           ("height", np.int16), ("width", np.int16), ("spanning", np.uint8)])
+SPANS_X, SPANS_Y = 1, 2
+
+
+def _records(arrays) -> np.ndarray:
+    universe, signature, cells, height, width, spanning = arrays
+    out = np.empty(len(universe), dtype=CLUSTER_RECORD)
+    for name, a in zip(CLUSTER_RECORD.names, (universe, signature, cells, height, width, spanning)):
+        out[name] = a
+    return out
+
+
+def cluster_name(signature: int) -> str:
+    """The name of a cluster signature - block, beehive, loaf, boat, tub, ship,
+    pond, blinker, toad, beacon, glider, traffic light and a few more, in every
+    phase and symmetric image - or its 16 hex digits."""
+    return native().cluster_name(int(signature))
+
+
+def cluster_signature(cells) -> int:
+    """The signature of the one cluster a 2-D array of 0/1 holds (any size,
+    plane semantics); ``RuntimeError`` when it holds none or several."""
+    g = np.asarray(cells)
+    if g.ndim != 2:
+        raise ValueError(f"cluster_signature: cells must be a 2-D array, got {g.ndim} dimensions")
+    if ((g != 0) & (g != 1)).any():
+        raise RuntimeError("cluster_signature: the array holds 0 (dead) and 1 (live) only")
+    return int(native().cluster_signature(np.ascontiguousarray(g.astype(np.uint8))))
+
+
+def cluster_table(records: np.ndarray) -> list[tuple]:
+    """Records aggregated to ``(signature, name, cells, height, width,
+    spanning, count)``, sorted by count descending, then signature."""
+    keys = ["signature", "cells", "height", "width", "spanning"]
+    if len(records) == 0:
+        return []
+    kinds, counts = np.unique(records[keys], return_counts=True)
+    order = np.lexsort((kinds["signature"], -counts))
+    return [(int(k["signature"]), cluster_name(int(k["signature"])), int(k["cells"]), int(k["height"]),
+             int(k["width"]), int(k["spanning"]), int(n)) for k, n in zip(kinds[order], counts[order])]
+
+
+def find_clusters(grids, boundary: str = DEFAULT_BOUNDARY, engine: str = "auto", *, threads: int = 0, device: int = 0,
+                  tune=None) -> tuple[np.ndarray, np.ndarray]:
+    """The cluster census of arbitrary 0/1 grids ``(B, H, W)`` of a batch
+    shape: ``(clusters, records)``, the number of clusters of every universe
+    (int32) and the ``CLUSTER_RECORD`` array, sorted by universe, then by each
+    cluster's smallest cell in row-major order.  The hip engine runs
+    csrc/kernels/life_batch_clusters.hip, the cpu engine a flood fill."""
+    C = native()
+    if engine == "auto":
+        engine = "hip" if C.hip_available() else "cpu"
+    if engine not in ("hip", "cpu"):
+        raise ValueError(f"unknown engine {engine!r} (want hip, cpu or auto)")
+    g = np.asarray(grids)
+    if g.ndim != 3:
+        raise ValueError(f"find_clusters: grids must be a (B, H, W) array, got {g.ndim} dimensions")
+    if g.dtype != np.uint8:
+        if ((g != 0) & (g != 1)).any():
+            raise RuntimeError("batch: the input holds 0 (dead) and 1 (live) only")
+        g = g.astype(np.uint8)
+    r = C.find_clusters(np.ascontiguousarray(g), boundary=str(boundary), engine=engine, threads=int(threads),
+                        device=int(device), tune=make_tuning(tune))
+    return r[0], _records(r[1:7])
+
 
 @dataclasses.dataclass
 class BatchResult:
@@ -31,7 +100,11 @@ class BatchResult:
     ``(B, H, W)``, each at its universe's own stop generation, or ``None``.
     ``kernel_ms``: the hip engine's one kernel (the cpu engine's loop).
     ``rules``: the canonical B/S strings of a ``rules=`` run (else ``None``);
-    ``soups``: its ``soups=K`` (else ``None``)."""
+    ``soups``: its ``soups=K`` (else ``None``).  With ``clusters=True``:
+    ``clusters``, the number of clusters of each final grid (int32),
+    ``cluster_records``, their ``CLUSTER_RECORD`` array sorted by universe, and
+    ``clusters_ms``, the census' two kernels (the cpu engine's wall time); else
+    ``None``."""
     generations: np.ndarray
     period: np.ndarray
     stop: np.ndarray
@@ -41,6 +114,22 @@ class BatchResult:
     variant: str
     rules: list[str] | None = None
     soups: int | None = None
+    clusters: np.ndarray | None = None
+    cluster_records: np.ndarray | None = None
+    clusters_ms: float | None = None
+
+    def cluster_table(self, stop=None) -> list[tuple]:
+        """The kinds of clusters: ``(signature, name, cells, height, width,
+        spanning, count)``, count descending, then signature.  ``stop``: a stop
+        reason or several (names or codes), to count only those universes."""
+        if self.cluster_records is None:
+            raise ValueError("cluster_table: the batch was not run with clusters=True")
+        recs = self.cluster_records
+        if stop is not None:
+            wanted = [stop] if isinstance(stop, (str, int, np.integer)) else list(stop)
+            codes = [BATCH_STOP.index(w) if isinstance(w, str) else int(w) for w in wanted]
+            recs = recs[np.isin(self.stop[recs["universe"]], codes)]
+        return cluster_table(recs)
 
     def stop_names(self) -> list[str]:
         return [BATCH_STOP[int(c)] for c in self.stop]
@@ -79,7 +168,7 @@ def life_like_rules() -> list[str]:
 def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens: int = 1024, max_period: int = 64,
                    rule: str = DEFAULT_RULE, boundary: str = DEFAULT_BOUNDARY, engine: str = "auto",
                    return_grids: bool = False, threads: int = 0, device: int = 0, tune=None, rules=None,
-                   soups=None) -> BatchResult:
+                   soups=None, clusters: bool = False) -> BatchResult:
     """Run ``B`` universes until each repeats or reaches ``max_gens``.
 
     Input: ``grids``, a ``(B, H, W)`` array of 0/1, or ``random=(seed,
@@ -106,7 +195,12 @@ def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens:
     1..65536, ``max_gens`` outside 1..2^24, B0 rules, cells other than 0/1,
     ``grids`` together with ``random``; on the hip engine a rule that is not
     compiled for it (``hip_rules()``; ``rules=[...]`` takes any).
-    ``engine="auto"``: hip where a device is available, else cpu (any rule)."""
+    ``engine="auto"``: hip where a device is available, else cpu (any rule).
+
+    ``clusters=True`` adds the cluster census of the final grids
+    (``BatchResult.clusters``, ``cluster_records``, ``cluster_table()``): live
+    cells at Chebyshev distance at most 2 belong to one cluster.  A call whose
+    records would exceed 2^28 is refused."""
     C = native()
     if grids is not None and (random is not None or batch is not None):
         raise ValueError("simulate_batch: give either grids or random=(seed, density) with batch=B, not both")
@@ -146,6 +240,8 @@ def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens:
     common = dict(max_gens=int(max_gens), max_period=int(max_period), rule=parse_rule(rule), boundary=str(boundary),
                   engine=engine, return_grids=bool(return_grids), threads=int(threads), device=int(device),
                   tune=make_tuning(tune))
+    if clusters:
+        common["clusters"] = True
     if grids is not None:
         g = np.asarray(grids)
         if g.ndim != 3:
@@ -164,4 +260,8 @@ def simulate_batch(grids=None, *, batch=None, shape=None, random=None, max_gens:
         W, H = shape
         r = C.simulate_batch(None, batch=int(batch), W=int(W), H=int(H), seed=int(seed), density=float(density),
                              **common, **extra)
-    return BatchResult(*r, rules=canon, soups=K)
+    census = {}
+    if clusters:
+        c = r[7]
+        census = dict(clusters=c[0], cluster_records=_records(c[1:7]), clusters_ms=float(c[7]))
+    return BatchResult(*r[:7], rules=canon, soups=K, **census)

@@ -32,7 +32,7 @@ BUILD = REPO / "build" / "obj"
 
 HOST_SRCS = ["src/decomp.cpp", "src/parallel.cpp", "src/backend_cpu.cpp", "src/transport.cpp",
              "src/engine.cpp", "src/io.cpp", "src/cpu_ref.cpp", "src/checkpoint.cpp", "src/tuning.cpp",
-             "src/numa.cpp", "src/batch_cpu.cpp"]
+             "src/numa.cpp", "src/batch_cpu.cpp", "src/batch_clusters.cpp"]
 # One translation unit per compiled kernel variant (layout x cross-lane
 # window), so the build compiles them in parallel.  The variants measured
 # slower than these (resident epochs, persistent dataflow launches, short
@@ -55,7 +55,8 @@ HIP_SRCS = ["src/backend_hip.hip", "src/transport_rccl.hip", "kernels/life_block
             *[f"kernels/life_block_{v}.hip" for v in LIFE_VARIANTS],
             *[f"kernels/life_rule_{v}.hip" for v in RULE_VARIANTS], "kernels/life_step_lds.hip",
             "kernels/tile_ops.hip", "kernels/view_ops.hip",
-            "kernels/life_batch.hip"]  # batched small universes (gol/batch.hpp)
+            "kernels/life_batch.hip",  # batched small universes (gol/batch.hpp)
+            "kernels/life_batch_clusters.hip"]  # their cluster census
 BIND_SRCS = ["src/bindings.cpp"]
 CLI_MAIN = "tools/gol_main.cpp"
 GEN_MAIN = "tools/gol_gen.cpp"
